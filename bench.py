@@ -1,6 +1,13 @@
 """Benchmark: GCN SpMM aggregation (the BASELINE.json metric) on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|ns] [--feat F]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line. ``--full`` adds
+everything else the benchmark measures beside the headline: the CPU baselines, the cache-cold
+step, the layer / training-step / model timings, the replay floor, the north star, cfg3 and
+cfg4 sub-objects and the detail sidecar. ``--dump-outputs DIR`` writes what the last timed step
+computed as DIR/<name>.npy (float32; a fixed seeded row sample when the output is large).
 
 One "step" = one full GCN neighbour aggregation Y = A_hat . X + b over the
 whole (per-rank) graph -- the op that replaces torch.spmm(adj, support) + bias
@@ -213,6 +220,31 @@ def gat_replay(ga, k: int, fn, reps: int = 5, table_rows: int = 2048) -> dict | 
                nonhub_gathers=int((~hub).sum()),
                method="product kernels on the real plan, gathered ids rewritten")
     return out
+
+
+DUMP_MAX_BYTES = 48_000_000  # all arrays of one --dump-outputs together (limit: 64 MB)
+
+
+def dump_outputs(args, arrays: dict, rank: int = 0, world: int = 1) -> None:
+    """--dump-outputs DIR: the tensors the timed path handed back in its last step, each as
+    DIR/<name>.npy (float32; DIR/<name>_rank<r>.npy at N ranks). An output larger than its share
+    of DUMP_MAX_BYTES is written as a row sample: sorted distinct rows drawn by
+    numpy.random.default_rng(0), the same rows in every run of the same arguments."""
+    if not args.dump_outputs:
+        return
+    out = Path(args.dump_outputs)
+    out.mkdir(parents=True, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(1, len(arrays))
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t.reshape(t.shape[0], -1) if t.dim() > 1 else t.reshape(-1, 1)
+        keep = max(1, share // (4 * t.shape[1]))
+        if t.shape[0] > keep:
+            rows = np.sort(np.random.default_rng(0).choice(t.shape[0], keep, replace=False))
+            t = t[torch.from_numpy(rows).to(t.device)]
+        a = np.ascontiguousarray(t.to(torch.float32).cpu().numpy())
+        np.save(out / (f"{name}.npy" if world == 1 else f"{name}_rank{rank}.npy"), a)
+        log(f"[bench] wrote {name} {a.shape} to {out}")
 
 
 BUILD_INFO = {}
@@ -593,22 +625,8 @@ def run_gat(args, dev, rank: int = 0, world: int = 1):
                                          a_dst=a_d))
            for m in (GAT_DENSE, GAT_SPARSE)}
     layer_ms, wall = time_steps(layer, args.steps, args.warmup, dev)
-    agg_ms = {m: time_steps(f, args.steps, args.warmup, dev)[0] for m, f in agg.items()}
-    proj_ms = time_steps(lambda: gat_project(X, W, H, Fh, a_s, a_d, col_rows=inv), args.steps,
-                         args.warmup, dev)[0]
+    dump_outputs(args, {"out": out})
     nnz, n = g.nnz, g.n_rows
-    from graphneuralnetwork_amd.ops import hub_rows_for
-    hub_k = hub_rows_for(g.n_cols, H * Fh + H)
-    # SURVEY 8(d) gather model (every gathered Wh row / er entry from HBM) and the compulsory
-    # bytes (each input read once, the output written once): col per edge; rowptr, el, the
-    # Wh row, the er entry and the output row per node
-    gm = nnz * (4 + 4 * H + 4 * H * Fh) + n * (8 + 4 * H + 4 * H * Fh)
-    comp = nnz * 4 + n * (8 + 4 * H + 4 * H + 4 * H * Fh + 4 * H * Fh)
-    k_ms = statistics.mean(agg_ms[GAT_DENSE])
-    t = k_ms / 1e3
-    achieved = comp / t / 1e9
-    tf = traffic_fields(ROOT / "profiles" / "traffic_cfg3_F64.json")
-    traffic = tf["traffic"]
     from graphneuralnetwork_amd.ops import transform_precision
     proj_arith = ("fp32 products from split-bf16 MFMAs (x and W in three bf16 pieces, six "
                   "v_mfma_f32_16x16x32_bf16 products accumulated in fp32)"
@@ -629,30 +647,50 @@ def run_gat(args, dev, rank: int = 0, world: int = 1):
                                           "projection writes Wh / er in that order (el in "
                                           "place); output rows in the original order"
                                           % order_s} if order is not None else {})},
-           "layer_ms": statistics.median(layer_ms),
-           "aggregate_ms": {"dense": statistics.median(agg_ms[GAT_DENSE]),
-                            "sparse": statistics.median(agg_ms[GAT_SPARSE])},
-           "project_ms": statistics.median(proj_ms), "project_arithmetic": proj_arith,
-           "project_tflops": 2.0 * n * Fin * (H * Fh + 2 * H) / (statistics.median(proj_ms) / 1e3)
-           / 1e12,
-           "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                        "frac": achieved / HBM_PEAK_GBPS, **tf,
-                        "compulsory_bytes": comp,
-                        "traffic_over_compulsory": traffic / comp if traffic else None,
-                        "gather_model_bytes": gm, "gather_model_GBps": gm / t / 1e9,
-                        "gather_model_frac": gm / t / 1e9 / HBM_PEAK_GBPS,
-                        "traffic_GBps": traffic / t / 1e9 if traffic else None,
-                        "traffic_frac": traffic / t / 1e9 / HBM_PEAK_GBPS if traffic else None,
-                        "kernel": (("gat_eh_kernel<dense, er from the rows> (segments, mid "
-                                    "and one-edge rows; the Wh rows of the %d highest-degree "
-                                    "columns read in place, the first rows in the column-degree "
-                                    "order) + " % hub_k) if order is not None
-                                   else ("gather_rows_kernel x2 (hub staging: Wh / er rows of "
-                                         "the %d highest-degree columns) + gat_eh_kernel<dense> + "
-                                         % hub_k) if hub_k else "gat_eh_kernel<dense> + ")
-                                  + "gat_short_kernel + gat_fixup_kernel",
-                        "avg_launch_ms": k_ms,
-                        "median_launch_ms": statistics.median(agg_ms[GAT_DENSE])}}
+           "layer_ms": statistics.median(layer_ms)}
+    if not args.full:  # the layer alone: the aggregation / projection runs and their roofline,
+        del Wh, out, Wh_o, el_o, er_o, g, X  # the CPU lines and the training step are --full's
+        torch.cuda.empty_cache()
+        return res
+    agg_ms = {m: time_steps(f, args.steps, args.warmup, dev)[0] for m, f in agg.items()}
+    proj_ms = time_steps(lambda: gat_project(X, W, H, Fh, a_s, a_d, col_rows=inv), args.steps,
+                         args.warmup, dev)[0]
+    from graphneuralnetwork_amd.ops import hub_rows_for
+    hub_k = hub_rows_for(g.n_cols, H * Fh + H)
+    # SURVEY 8(d) gather model (every gathered Wh row / er entry from HBM) and the compulsory
+    # bytes (each input read once, the output written once): col per edge; rowptr, el, the
+    # Wh row, the er entry and the output row per node
+    gm = nnz * (4 + 4 * H + 4 * H * Fh) + n * (8 + 4 * H + 4 * H * Fh)
+    comp = nnz * 4 + n * (8 + 4 * H + 4 * H + 4 * H * Fh + 4 * H * Fh)
+    k_ms = statistics.mean(agg_ms[GAT_DENSE])
+    t = k_ms / 1e3
+    achieved = comp / t / 1e9
+    tf = traffic_fields(ROOT / "profiles" / "traffic_cfg3_F64.json")
+    traffic = tf["traffic"]
+    res.update({
+        "aggregate_ms": {"dense": statistics.median(agg_ms[GAT_DENSE]),
+                         "sparse": statistics.median(agg_ms[GAT_SPARSE])},
+        "project_ms": statistics.median(proj_ms), "project_arithmetic": proj_arith,
+        "project_tflops": 2.0 * n * Fin * (H * Fh + 2 * H) / (statistics.median(proj_ms) / 1e3)
+        / 1e12,
+        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                     "frac": achieved / HBM_PEAK_GBPS, **tf,
+                     "compulsory_bytes": comp,
+                     "traffic_over_compulsory": traffic / comp if traffic else None,
+                     "gather_model_bytes": gm, "gather_model_GBps": gm / t / 1e9,
+                     "gather_model_frac": gm / t / 1e9 / HBM_PEAK_GBPS,
+                     "traffic_GBps": traffic / t / 1e9 if traffic else None,
+                     "traffic_frac": traffic / t / 1e9 / HBM_PEAK_GBPS if traffic else None,
+                     "kernel": (("gat_eh_kernel<dense, er from the rows> (segments, mid "
+                                 "and one-edge rows; the Wh rows of the %d highest-degree "
+                                 "columns read in place, the first rows in the column-degree "
+                                 "order) + " % hub_k) if order is not None
+                                else ("gather_rows_kernel x2 (hub staging: Wh / er rows of "
+                                      "the %d highest-degree columns) + gat_eh_kernel<dense> + "
+                                      % hub_k) if hub_k else "gat_eh_kernel<dense> + ")
+                               + "gat_short_kernel + gat_fixup_kernel",
+                     "avg_launch_ms": k_ms,
+                     "median_launch_ms": statistics.median(agg_ms[GAT_DENSE])}})
     if not args.no_replay and order is not None:
         rpf = gat_replay(ga, hub_k, agg[GAT_DENSE])
         if rpf is not None:
@@ -918,6 +956,8 @@ def run_gat_edgecut(args, dev, rank: int, world: int):
     dist.barrier()
     step_ms, wall = time_steps(step, args.steps, 0, dev)
     dist.barrier()
+    if args.dump_outputs:  # the same inputs give the last timed step's output again
+        dump_outputs(args, {"out": step()}, rank, world)
     phase("reduce", 120)
     red = torch.tensor([wall, float(nnz_local), statistics.median(step_ms)], dtype=torch.float64,
                        device=dev if dist.get_backend() == "nccl" else "cpu")
@@ -989,8 +1029,13 @@ def run_sage(args, dev, rank: int = 0, world: int = 1, edges_np=None):
         phase("timed_steps", 300)
         if world > 1:
             dist.barrier()
-        fwd_ms, wall = time_steps(lambda: net(*fargs, None, None, None, None, None), args.steps,
-                                  args.warmup, dev)
+        forward = lambda: net(*fargs, None, None, None, None, None)  # noqa: E731
+        if args.dump_outputs:  # keep what the last forward returned: (embeddings, logits)
+            last, run = {}, forward
+            forward = lambda: last.__setitem__("y", run())  # noqa: E731
+        fwd_ms, wall = time_steps(forward, args.steps, args.warmup, dev)
+        if args.dump_outputs:
+            dump_outputs(args, dict(zip(("embeddings", "logits"), last.pop("y"))), rank, world)
         edges_all = batch.sampled_edges
         if world > 1:
             dist.barrier()
@@ -1001,6 +1046,31 @@ def run_sage(args, dev, rank: int = 0, world: int = 1, edges_np=None):
             dist.all_reduce(mx, op=dist.ReduceOp.MAX)
             dist.all_reduce(red[1:], op=dist.ReduceOp.SUM)
             wall, edges_all = float(mx.item()), int(red[1].item())
+        M, k1 = batch.frontier_nbrs.shape
+        B, k0 = batch.neigh_map.shape
+        edges = batch.sampled_edges
+        res = {"metric": "GraphSAGE sampled-neighbour aggregated edges/sec (2-layer forward)",
+               "value": edges_all * args.steps / wall, "unit": "edges/s", "n_gpus": world,
+               "steps": args.steps, "warmup": args.warmup, "ms_per_step": wall / args.steps * 1e3,
+               "higher_is_better": True,
+               "scaling": "weak", "vs_baseline": None, "dtype": "fp32", "data": "synthetic R-MAT",
+               "config": {"workload": wl["name"], "nodes": n, "adj_nnz": adj.nnz, "seeds": B,
+                          "frontier": M, "fanout": [k0, k1], "sampled_edges": edges, "feat_dim": F,
+                          "step": "GraphSAGE.forward (one [self | mean] gather launch + one K=2F "
+                                  "GEMM per SageLayer, classifier) on device-sampled index maps",
+                          "sage_layer_gemm": transform_note(),
+                          "node_order": "dataset relabelled once by degree "
+                                        "(sampler.degree_ordered, %.2f s, outside the timed "
+                                        "region); seeds drawn in the new ids" % order_s},
+               "forward_ms": statistics.median(fwd_ms),
+               "median_step_ms": statistics.median(fwd_ms), "first_sample_s": t_sample}
+        if world > 1:
+            res["config"]["global_seeds"] = 8192 * world
+            res["config"]["parallelism"] = f"seed-sharded{world} (replicated table, no collective)"
+        if not args.full:  # the forward alone: the kernel / sampler / batch timings, the
+            del table, adj, batch, fargs  # roofline, the variants and the CPU lines are --full's
+            torch.cuda.empty_cache()
+            return res
         phase("extras", None)
         agg_ms, _ = time_steps(lambda: sage_gather_aggregate(table, batch.frontier_nbrs, "MEAN",
                                                              check=False),
@@ -1073,9 +1143,6 @@ def run_sage(args, dev, rank: int = 0, world: int = 1, edges_np=None):
             graph_ms = statistics.mean(graph_ms)
         except Exception as e:  # reported, never the headline
             log(f"[bench] graph capture of the forward failed: {e!r}")
-    M, k1 = batch.frontier_nbrs.shape
-    B, k0 = batch.neigh_map.shape
-    edges = batch.sampled_edges
     # layer-0 gather-mean: the 8(d) gather model counts every gathered row; the compulsory
     # bytes count each distinct table row once (+ the index map and the output)
     bytes_l0 = M * k1 * (4 * F + 8) + M * 4 * F
@@ -1086,48 +1153,31 @@ def run_sage(args, dev, rank: int = 0, world: int = 1, edges_np=None):
     achieved = comp_l0 / t / 1e9
     tf = traffic_fields(ROOT / "profiles" / f"traffic_cfg4_F{F}.json")
     traffic = tf["traffic"]
-    res = {"metric": "GraphSAGE sampled-neighbour aggregated edges/sec (2-layer forward)",
-           "value": edges_all * args.steps / wall, "unit": "edges/s", "n_gpus": world,
-           "steps": args.steps,
-           "warmup": args.warmup, "ms_per_step": wall / args.steps * 1e3, "higher_is_better": True,
-           "scaling": "weak", "vs_baseline": None, "dtype": "fp32", "data": "synthetic R-MAT",
-           "config": {"workload": wl["name"], "nodes": n, "adj_nnz": adj.nnz, "seeds": B,
-                      "frontier": M, "fanout": [k0, k1], "sampled_edges": edges, "feat_dim": F,
-                      "step": "GraphSAGE.forward (one [self | mean] gather launch + one K=2F "
-                              "GEMM per SageLayer, classifier) on device-sampled index maps",
-                      "sage_layer_gemm": transform_note(),
-                      "node_order": "dataset relabelled once by degree (sampler.degree_ordered, "
-                                    "%.2f s, outside the timed region); seeds drawn in the new "
-                                    "ids" % order_s},
-           "forward_ms": statistics.median(fwd_ms), "sample_ms": statistics.median(smp_ms),
-           "batch_ms": statistics.median(batch_ms),
-           "batch_ms_note": "sample_batch(sync=False) + forward: the layer sizes stay on the "
-                            "device, every batch's error word is read after the timed steps",
-           "batch_synced_ms": statistics.median(batch_synced_ms),
-           "sample_pending_ms": statistics.median(smp_pending_ms),
-           "median_step_ms": statistics.median(fwd_ms),
-           "forward_hipgraph_ms": graph_ms,
-           "first_sample_s": t_sample,
-           "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                        "frac": achieved / HBM_PEAK_GBPS, **tf,
-                        "compulsory_bytes": comp_l0, "distinct_rows": distinct,
-                        "traffic_over_compulsory": traffic / comp_l0 if traffic else None,
-                        "gather_model_bytes": bytes_l0, "gather_model_GBps": bytes_l0 / t / 1e9,
-                        "gather_model_frac": bytes_l0 / t / 1e9 / HBM_PEAK_GBPS,
-                        "traffic_GBps": traffic / t / 1e9 if traffic else None,
-                        "traffic_frac": traffic / t / 1e9 / HBM_PEAK_GBPS if traffic else None,
-                        "kernel": "sage_aggregate_kernel<gather, mean> (layer 0: |S1| x 10 from the 10M table)"
-                                  + (", %d launches per HIP-graph replay" % REP if agg_graph_ms else
-                                     ", eager per-launch HIP events"),
-                        "eager_launch_ms": statistics.median(agg_ms),
-                        "avg_launch_ms": k_ms,
-                        "median_launch_ms": statistics.median(agg_graph_ms or agg_ms)}}
+    res.update({
+        "sample_ms": statistics.median(smp_ms),
+        "batch_ms": statistics.median(batch_ms),
+        "batch_ms_note": "sample_batch(sync=False) + forward: the layer sizes stay on the "
+                         "device, every batch's error word is read after the timed steps",
+        "batch_synced_ms": statistics.median(batch_synced_ms),
+        "sample_pending_ms": statistics.median(smp_pending_ms),
+        "forward_hipgraph_ms": graph_ms,
+        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                     "frac": achieved / HBM_PEAK_GBPS, **tf,
+                     "compulsory_bytes": comp_l0, "distinct_rows": distinct,
+                     "traffic_over_compulsory": traffic / comp_l0 if traffic else None,
+                     "gather_model_bytes": bytes_l0, "gather_model_GBps": bytes_l0 / t / 1e9,
+                     "gather_model_frac": bytes_l0 / t / 1e9 / HBM_PEAK_GBPS,
+                     "traffic_GBps": traffic / t / 1e9 if traffic else None,
+                     "traffic_frac": traffic / t / 1e9 / HBM_PEAK_GBPS if traffic else None,
+                     "kernel": "sage_aggregate_kernel<gather, mean> (layer 0: |S1| x 10 from the 10M table)"
+                               + (", %d launches per HIP-graph replay" % REP if agg_graph_ms else
+                                  ", eager per-launch HIP events"),
+                     "eager_launch_ms": statistics.median(agg_ms),
+                     "avg_launch_ms": k_ms,
+                     "median_launch_ms": statistics.median(agg_graph_ms or agg_ms)}})
     if world == 1 and not args.no_variants:
         res["aggregators"] = sage_aggregator_variants(args, dev, table, batch, fargs, F, H,
                                                       distinct)
-    if world > 1:
-        res["config"]["global_seeds"] = 8192 * world
-        res["config"]["parallelism"] = f"seed-sharded{world} (replicated table, no collective)"
     if not args.no_cpu_baseline and world == 1:
         from oracle import c_oracle
         threads = cpu_threads()
@@ -1596,6 +1646,9 @@ def run_gcn(args, dev, rank: int, world: int, workload: str, edges_np=None, extr
         X = torch.randn(part.n_own, F, device=dev, generator=gen)
         runner = EdgeCutSpmm(part, F, dev)
         step = lambda: runner(X, bias)  # noqa: E731
+        if args.dump_outputs:  # keep what the last step returned
+            last, run = {}, step
+            step = lambda: last.__setitem__("Y", run())  # noqa: E731
         r0, r1 = part.bounds[rank], part.bounds[rank + 1]
         rows_local = part.n_own
         nnz_local = int(g.rowptr[r1] - g.rowptr[r0])        # graph edges of the owned rows
@@ -1643,6 +1696,8 @@ def run_gcn(args, dev, rank: int, world: int, workload: str, edges_np=None, extr
     wall = time.perf_counter() - t0
     gpu_ms = ev0.elapsed_time(ev1)
     step_ms = [a.elapsed_time(b) for a, b in per_step]
+    if args.dump_outputs and not extras:  # Y: what the last timed step wrote / returned
+        dump_outputs(args, {"Y": Y if world == 1 else last["Y"]}, rank, world)
     phase("reduce", 120)
     elapsed = torch.tensor([max(wall, gpu_ms / 1e3)], dtype=torch.float64, device=dev)
     tot_nnz = torch.tensor([nnz_local], dtype=torch.float64, device=dev)
@@ -1674,7 +1729,7 @@ def run_gcn(args, dev, rank: int, world: int, workload: str, edges_np=None, extr
         torch.cuda.empty_cache()
         log(f"[bench] {workload} cache-cold step (1 GiB written before each): {cold:.3f} ms")
     phases = None
-    if world > 1 and dev.type == "cuda":
+    if world > 1 and dev.type == "cuda" and args.full:
         # one more (untimed) step with events at every phase boundary: per-rank compute
         # phases, the compute stream's waits on the exchanges, and the all-to-all-v times
         phase("phase_profile", 180)
@@ -1969,10 +2024,19 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default=None, choices=sorted(WORKLOADS),
-                    help="one workload only (default: cfg2 as the headline, plus the north "
-                         "star, cfg3 and cfg4 as sub-objects at N=1)")
+                    help="one workload only (default: cfg2 as the headline; with --full plus the "
+                         "north star, cfg3 and cfg4 as sub-objects at N=1)")
     ap.add_argument("--feat", type=int, default=None,
                     help="feature width (default: the workload's, 128 except cfg5 = 256)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline too: CPU baselines, the cache-cold step, "
+                         "layer / training-step / model timings, the replay floor, per-kernel "
+                         "rooflines that take runs of their own, the north_star / cfg3 / cfg4 "
+                         "sub-objects, the N-rank phase profile and the detail sidecar (the "
+                         "--no-* options below switch parts of it off)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32; a "
+                         "fixed seeded row sample of an output over its share of 48 MB)")
     ap.add_argument("--no-extras", action="store_true",
                     help="headline only (no north_star / cfg3 / cfg4 sub-objects)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -2003,6 +2067,12 @@ def main():
     ap.add_argument("--traffic-json", default=None,
                     help="PMC traffic summary (tools/pmc_traffic.py); default profiles/traffic_<workload>_F<feat>.json")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:  # a plain run: set up, warm up, time the steps, print the line
+        for k in ("extras", "cpu_baseline", "cold", "layer", "train", "variants", "replay",
+                  "cpu_reference"):
+            setattr(args, "no_" + k, True)
     # stdout carries exactly ONE line, the JSON result: whatever the libraries print there
     # (RCCL's version banner at communicator init, gloo's peer messages) goes to stderr with
     # the bench's own log lines
@@ -2046,6 +2116,7 @@ def main():
         res = run_sage(args, dev, rank, world)
     else:
         res = run_gcn(args, dev, rank, world, workload)
+    args.dump_outputs = None  # the headline's outputs only
     if extras:
         # the other BASELINE configs that fit one GPU, timed in the same driver run: the north
         # star (10M / 100M, F=128), cfg3 (GAT) and cfg4 (GraphSAGE). The 10M / 100M R-MAT edge
@@ -2068,7 +2139,9 @@ def main():
     if rank == 0:
         res["bench_wall_s"] = time.perf_counter() - t_all
         res.update(library_stamps())
-        line = compact_line(res, write_detail(res, world))
+        # the sidecar holds what --full measured; a plain run writes one only where asked
+        detail = args.full or os.environ.get("GNN_BENCH_DETAIL")
+        line = compact_line(res, write_detail(res, world) if detail else None)
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(line) + "\n").encode())
     if world > 1:

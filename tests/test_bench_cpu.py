@@ -85,3 +85,26 @@ def test_write_detail_sidecar(tmp_path, monkeypatch):
     monkeypatch.setenv("GNN_BENCH_DETAIL", str(tmp_path / "d.json"))
     name = bench.write_detail({"value": 1.0, "big": list(range(10))}, 1)
     assert json.loads(Path(name).read_text())["big"][-1] == 9
+
+
+def test_dump_outputs_row_sample_is_fixed(tmp_path, monkeypatch):
+    """--dump-outputs: float32 .npy files; an output over its share of DUMP_MAX_BYTES is written
+    as the same sorted, distinct rows in every run; a small one whole."""
+    import argparse
+
+    import numpy as np
+    sys.path.insert(0, str(ROOT))
+    import bench
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 2 * 40 * 16 * 4)  # 40 rows of 16 floats each
+    big = torch.arange(1000 * 16, dtype=torch.float64).reshape(1000, 16)
+    small = torch.arange(12, dtype=torch.float32).reshape(3, 4)
+    for d in ("a", "b"):
+        bench.dump_outputs(argparse.Namespace(dump_outputs=str(tmp_path / d)),
+                           {"big": big, "small": small})
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a.dtype == np.float32 and a.shape == (40, 16) and np.array_equal(a, b)
+    rows = (a[:, 0] / 16).astype(np.int64)
+    assert np.all(np.diff(rows) > 0) and np.array_equal(a, big.numpy()[rows].astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / "a" / "small.npy"), small.numpy())
+    bench.dump_outputs(argparse.Namespace(dump_outputs=None), {"big": big})  # off: no file
+    assert sorted(p.name for p in tmp_path.iterdir()) == ["a", "b"]

@@ -15,6 +15,8 @@ for wl in ${WORKLOADS:-cfg2 ns cfg3 cfg4}; do
 done
 if [ -z "${NO_BENCH:-}" ]; then
   echo "== default bench ($(date +%T))"
-  timeout -k 10 600 python3 -u bench.py > gpurun_out/bench_default.json 2> gpurun_out/bench_default.err
+  OUT=${OUT:-build/bench}
+  mkdir -p "$OUT"
+  timeout -k 10 600 python3 -u bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
 fi
 echo "== done ($(date +%T))"
