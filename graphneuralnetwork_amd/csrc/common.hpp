@@ -45,8 +45,11 @@ __device__ __forceinline__ f4 shfl_xor_f(f4 v, int m) {
             __shfl_xor(v.w, m, kWave)};
 }
 
+// torch.relu: NaN stays NaN (fmaxf(NaN, 0) would return 0); one compare and one select
+__device__ __forceinline__ float relu_nan(float v) { return (v > 0.f || v != v) ? v : 0.f; }
+
 __device__ __forceinline__ float act_apply(float v, uint32_t flags) {
-  if (flags & GNN_EPI_RELU) v = (v > 0.f || v != v) ? v : 0.f;  // torch.relu: NaN stays NaN
+  if (flags & GNN_EPI_RELU) v = relu_nan(v);
   if (flags & GNN_EPI_ELU) v = v > 0.f ? v : expm1f(v);
   return v;
 }

@@ -377,10 +377,12 @@ __global__ __launch_bounds__(kTnThreads, 2) void gemm_tn_x6_kernel(
       const int e = t + q * kTnThreads;
       if constexpr (MB) {  // after the wait for the tile: no stall on the prefetch
         const float4 h = vd[q];
-        vb[q].x = h.x > 0.f ? vb[q].x * mscale : 0.f;
-        vb[q].y = h.y > 0.f ? vb[q].y * mscale : 0.f;
-        vb[q].z = h.z > 0.f ? vb[q].z * mscale : 0.f;
-        vb[q].w = h.w > 0.f ? vb[q].w * mscale : 0.f;
+        // a product, as the Dropout backward is (dy * mask): a NaN gradient stays NaN at a
+        // masked element instead of turning into 0
+        vb[q].x *= h.x > 0.f ? mscale : 0.f;
+        vb[q].y *= h.y > 0.f ? mscale : 0.f;
+        vb[q].z *= h.z > 0.f ? mscale : 0.f;
+        vb[q].w *= h.w > 0.f ? mscale : 0.f;
       }
       if (e < kTnRows * B4) sb[(e / B4) * (PB / 4) + e % B4] = vb[q];
       if constexpr (DSUM) {

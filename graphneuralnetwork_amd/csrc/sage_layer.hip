@@ -161,7 +161,7 @@ __global__ __launch_bounds__(kSlBlock) __attribute__((amdgpu_waves_per_eu(H == 1
         for (int cb = 0; cb < CB; ++cb) {
           const sl32x4 y = d[rb][0][cb] + d[rb][1][cb];
           *reinterpret_cast<f4*>(out + orow * ldo + (wv * CB + cb) * 16 + 4 * q) =
-              f4{fmaxf(y[0], 0.f), fmaxf(y[1], 0.f), fmaxf(y[2], 0.f), fmaxf(y[3], 0.f)};
+              f4{relu_nan(y[0]), relu_nan(y[1]), relu_nan(y[2]), relu_nan(y[3])};
         }
       }
     }

@@ -354,17 +354,18 @@ __global__ __launch_bounds__(NW * kWave) void gcn_transform_kernel(
             o.w += bv.w;
           }
           if constexpr (RELU) {
-            o.x = fmaxf(o.x, 0.f);
-            o.y = fmaxf(o.y, 0.f);
-            o.z = fmaxf(o.z, 0.f);
-            o.w = fmaxf(o.w, 0.f);
+            o.x = relu_nan(o.x);  // nn.ReLU: a NaN activation stays NaN
+            o.y = relu_nan(o.y);
+            o.z = relu_nan(o.z);
+            o.w = relu_nan(o.w);
           }
           if (epi.drop_p > 0.f) {  // uniform: inverted dropout, one hash per element
+            // a dropped element is x * 0 as in nn.Dropout: NaN stays NaN, a dropped inf is NaN
             const int c = epi.col0 + col;
-            o.x = dropout_keep(epi.seed, orow, c, epi.drop_p) ? o.x * epi.drop_scale : 0.f;
-            o.y = dropout_keep(epi.seed, orow, c + 1, epi.drop_p) ? o.y * epi.drop_scale : 0.f;
-            o.z = dropout_keep(epi.seed, orow, c + 2, epi.drop_p) ? o.z * epi.drop_scale : 0.f;
-            o.w = dropout_keep(epi.seed, orow, c + 3, epi.drop_p) ? o.w * epi.drop_scale : 0.f;
+            o.x *= dropout_keep(epi.seed, orow, c, epi.drop_p) ? epi.drop_scale : 0.f;
+            o.y *= dropout_keep(epi.seed, orow, c + 1, epi.drop_p) ? epi.drop_scale : 0.f;
+            o.z *= dropout_keep(epi.seed, orow, c + 2, epi.drop_p) ? epi.drop_scale : 0.f;
+            o.w *= dropout_keep(epi.seed, orow, c + 3, epi.drop_p) ? epi.drop_scale : 0.f;
           }
           *reinterpret_cast<float4*>(y + orow * ldy + (wv * CB + cb) * 16 + 4 * q) = o;
         }
@@ -377,7 +378,7 @@ __global__ __launch_bounds__(NW * kWave) void gcn_transform_kernel(
         for (int cb = 0; cb < CB; ++cb)
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
-            const float v = RELU ? fmaxf(acc[j][cb][i], 0.f) : acc[j][cb][i];
+            const float v = RELU ? relu_nan(acc[j][cb][i]) : acc[j][cb][i];
 #pragma unroll
             for (int c = 0; c < kMaxCls; ++c) pc[c] = fmaf(v, wd[cb][i][c], pc[c]);
           }

@@ -167,6 +167,19 @@ def _dropout_seed() -> int:
     return int(torch.randint(0, 2 ** 62, (1,)).item())
 
 
+def _all_dropped(Wh, g, mode, activation):
+    """The layer's output under attention dropout p = 1 (the kernels take p in [0, 1) only):
+    F.dropout(attention, 1.0) zeroes every coefficient, so h' = 0 @ Wh (layers.py:31-32) --
+    zero in every row, NaN in a column where Wh is not finite -- and the sparse layer divides
+    by e_rowsum (layers.py:115-122): 0 / 0 = NaN on an edgeless row. ELU(0) = 0 and ELU(NaN)
+    = NaN: ``activation`` changes nothing. Differentiable (zero gradients) like torch's."""
+    out = Wh.sum(0, keepdim=True) * Wh.new_zeros((g.n_rows, 1))
+    if mode == GAT_SPARSE and g.has_empty_rows():
+        empty = (g.rowptr[1:] - g.rowptr[:-1]) == 0
+        out = out.masked_fill(empty[:, None], float("nan"))
+    return out
+
+
 class _AttentionBase(nn.Module):
     MODE = GAT_DENSE
     PREDICATE = "positive"
@@ -183,8 +196,10 @@ class _AttentionBase(nn.Module):
         mask the backward prep applies; else model_dropout on the output)."""
         g = as_csr(adj, self.PREDICATE)
         p = dropout_p if self.training else 0.0
-        seed = _dropout_seed() if p > 0 else 0
-        if torch.is_grad_enabled() and (Wh.requires_grad or a_src.requires_grad
+        seed = _dropout_seed() if 0 < p < 1 else 0
+        if p >= 1:
+            out = _all_dropped(Wh, g, self.MODE, activation)
+        elif torch.is_grad_enabled() and (Wh.requires_grad or a_src.requires_grad
                                         or a_dst.requires_grad):
             fp = _padded_fh(heads, fh, Wh)
             if fp != fh:

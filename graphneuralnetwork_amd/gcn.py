@@ -139,7 +139,7 @@ def _no_hooks(*mods) -> bool:
 def _fuse_train(block, nxt, nxt2, X, adj) -> int:
     """How many modules from ``block`` run as one training op (0: none): 3 for
     Graph_conv_layer -> nn.ReLU -> nn.Dropout, 2 for Graph_conv_layer -> nn.ReLU (a Dropout
-    with hooks runs on its own), when the layer trains in the reassociated form on a transform
+    with hooks, or with p = 1, runs on its own), when the layer trains in the reassociated form on a transform
     shape (ops.fuses_relu_dropout) and none of the fused modules has hooks (they would not run).
     """
     if not (isinstance(block, Graph_conv_layer) and type(nxt) is nn.ReLU
@@ -152,7 +152,9 @@ def _fuse_train(block, nxt, nxt2, X, adj) -> int:
     if X.dim() != 2 or X.shape[1] != block.in_features or not fuses_relu_dropout(
             X, block.dense.weight, g):
         return 0
-    return 3 if type(nxt2) is nn.Dropout and _no_hooks(nxt2) else 2
+    # nn.Dropout(1.0) zeroes everything; the hashed epilogue takes p in [0, 1) only (its scale
+    # is 1 / (1 - p)), so that Dropout stays with torch
+    return 3 if type(nxt2) is nn.Dropout and _no_hooks(nxt2) and nxt2.p < 1 else 2
 
 
 def _fuse_relu(block, nxt, X) -> bool:

@@ -553,6 +553,10 @@ def gemm_tn(a: torch.Tensor, b: torch.Tensor, d: torch.Tensor | None = None,
         return None
 
     def fits(t):
+        # rows that overlap (a row stride below the row length: an expanded row, an as_strided
+        # window) are copied out; a single row has no second row to overlap
+        if n > 1 and t.stride(0) < t.shape[1]:
+            return False
         if kind == 2:  # narrow shapes: any row stride, unit column stride
             return (t.stride(1) == 1 or t.shape[1] == 1) and t.data_ptr() % 4 == 0
         return t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0
@@ -569,13 +573,22 @@ def gemm_tn(a: torch.Tensor, b: torch.Tensor, d: torch.Tensor | None = None,
     dsum = torch.empty(k, dtype=torch.float32, device=a.device) if d is not None else None
     ws = torch.empty(int(lib.gnn_gemm_tn_workspace_bytes(n, m, k)), dtype=torch.uint8,
                      device=a.device)
-    _lib.check(lib.gnn_gemm_tn_f32(a.data_ptr(), max(a.stride(0), m), b.data_ptr(),
-                                   max(b.stride(0), k), n, m, k, c.data_ptr(), c.stride(0),
-                                   1 if trans else 0, _lib.ptr(d),
-                                   max(d.stride(0), k) if d is not None else 0, _lib.ptr(dsum),
+
+    def ld(t):  # the row stride; of a single row (whose stride is never used) the row length
+        return t.stride(0) if n > 1 else t.shape[1]
+
+    _lib.check(lib.gnn_gemm_tn_f32(a.data_ptr(), ld(a), b.data_ptr(), ld(b), n, m, k,
+                                   c.data_ptr(), c.stride(0), 1 if trans else 0, _lib.ptr(d),
+                                   ld(d) if d is not None else 0, _lib.ptr(dsum),
                                    ws.data_ptr(), ws.numel(), _lib.stream_handle(a.device)),
                "gnn_gemm_tn_f32")
     return c, dsum
+
+
+def _masked_grad(gy: torch.Tensor, h: torch.Tensor, scale: float) -> torch.Tensor:
+    """gy . [h > 0] * scale as a product (what the Dropout backward computes: dy * mask), so a
+    NaN gradient stays NaN at a masked element; the masked gemm_tn kernel forms the same."""
+    return gy * torch.where(h > 0, float(scale), 0.0).to(gy.dtype)
 
 
 def gemm_tn_masked(a: torch.Tensor, b: torch.Tensor, h: torch.Tensor, scale: float,
@@ -591,9 +604,10 @@ def gemm_tn_masked(a: torch.Tensor, b: torch.Tensor, h: torch.Tensor, scale: flo
     ok = (a.dtype == b.dtype == h.dtype == torch.float32 and h.shape == b.shape
           and lib.gnn_gemm_tn_masked_supported(m, k)
           and all(t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0
+                  and t.stride(0) >= t.shape[1]  # no overlapping rows (expanded, as_strided)
                   for t in (a, b, h)))
     if not ok:
-        bm = torch.where(h > 0, b * scale, torch.zeros((), dtype=b.dtype, device=b.device))
+        bm = _masked_grad(b, h, scale)
         return gemm_tn(a, bm, bm if want_dsum else None, trans=trans)
     c = torch.empty((k, m) if trans else (m, k), dtype=torch.float32, device=a.device)
     dsum = torch.empty(k, dtype=torch.float32, device=a.device) if want_dsum else None
@@ -626,7 +640,7 @@ def linear_small(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor | None:
     # profiles/r06y_gcn_model_train_step_kernel_stats.csv): 128 and 256 stay on torch.mm
     if not kind or (kind == 2 and fout > LINEAR_SMALL_MAX_FOUT):
         return None
-    if x.stride(1) != 1 or x.stride(0) % 4 or x.data_ptr() % 16:
+    if x.stride(1) != 1 or x.stride(0) % 4 or x.data_ptr() % 16 or x.stride(0) < k:
         # rows copied to a 16-B aligned pitch (a multiple of 4 floats >= k)
         xp = torch.empty((x.shape[0], k + (-k) % 4), dtype=torch.float32, device=x.device)
         xp[:, :k] = x
@@ -688,10 +702,12 @@ GCN_FUSE_RELU_DROPOUT = True
 
 def fuses_relu_dropout(x, weight, g) -> bool:
     """Whether ``gcn_layer(..., relu_dropout=...)`` applies to this layer: the reassociated form
-    (``_reassociate``) on a shape the MFMA transform takes."""
+    (``_reassociate``) on a shape ``gcn_transform`` takes (its own conditions, restated)."""
     fout, fin = weight.shape
     return (GCN_FUSE_RELU_DROPOUT and _reassociate(x, weight, g)
-            and bool(_lib.load().gnn_gcn_transform_supported(fin, fout)))
+            and x.dtype == torch.float32 and weight.dtype == torch.float32
+            and bool(_lib.load().gnn_gcn_transform_supported(fin, fout))
+            and not (fout == 256 and fin > 64 and not TRANSFORM_WIDE_MFMA))
 
 
 def dropout_seed() -> int:
@@ -783,8 +799,7 @@ class _GcnLayerFn(torch.autograd.Function):
             dy = None
             if (ctx.needs_input_grad[1] and gw is None) or (want_b and gb is None) \
                     or ctx.needs_input_grad[0]:
-                dy = torch.where(h > 0, gy * scale, torch.zeros((), dtype=gy.dtype,
-                                                                device=gy.device))
+                dy = _masked_grad(gy, h, scale)
             if ctx.needs_input_grad[1] and gw is None:
                 gw = torch.mm(dy.t(), z)
             if want_b and gb is None:
@@ -900,8 +915,8 @@ def gat_project(x: torch.Tensor, w: torch.Tensor, heads: int, fh: int, a_src: to
     k, fout = w.shape
     if not lib.gnn_gat_project_supported(k, fout, fh):
         return None
-    if x.stride(1) != 1 or x.stride(0) % 4 or x.data_ptr() % 16:
-        x = x.contiguous()
+    if not _rows16(x) or x.stride(0) < k:  # rows the 16-B loads cannot take, or that overlap
+        x = x.clone(memory_format=torch.contiguous_format)
     n = x.shape[0]
     if col_rows is not None:
         _require_device(col_rows)
@@ -1018,8 +1033,8 @@ def gcn_transform(x: torch.Tensor, weight: torch.Tensor, relu: bool = False,
             raise ValueError("live= is supported with the ReLU epilogue (the SageLayer) only")
         if live.dtype != torch.int64 or live.numel() != 1:
             raise TypeError("live must be a one-element int64 device tensor")
-    if x.stride(1) != 1 or x.stride(0) % 4 or x.data_ptr() % 16:
-        x = x.contiguous()
+    if not _rows16(x) or x.stride(0) < k:  # rows the 16-B loads cannot take, or that overlap
+        x = x.clone(memory_format=torch.contiguous_format)
     w = weight.contiguous()
     m = x.shape[0]
     if out is None:
@@ -1085,8 +1100,8 @@ def linear_relu_classify(x: torch.Tensor, weight: torch.Tensor, wd: torch.Tensor
     if bd is not None:
         _require_device(bd)
         bd = bd.contiguous()
-    if x.stride(1) != 1 or x.stride(0) % 4 or x.data_ptr() % 16:
-        x = x.contiguous()
+    if not _rows16(x) or x.stride(0) < k:  # rows the 16-B loads cannot take, or that overlap
+        x = x.clone(memory_format=torch.contiguous_format)
     w, wdc = weight.contiguous(), wd.contiguous()
     m = x.shape[0]
     if out is None:
