@@ -56,6 +56,37 @@ SIGNATURES: dict[str, tuple] = {
         _vp, _vp, _i64,                 # long_row, long_seg_ptr, n_long
         _vp, _i64, _vp, _i64,           # mid_row, n_mid, task_row, n_task
         _vp, _u32, _vp]),               # partial, flags, stream
+    "gnn_spmm_csr_bf16": (ctypes.c_int, [
+        _vp, _vp, _vp, _i64,            # rowptr, col, val, n_rows
+        _vp, _i64, _i64,                # x (bf16), ldx, feat
+        _vp, _vp, _i64,                 # bias, y, ldy
+        _i64, _vp, _vp, _i64,           # seg_len, seg_row, seg_begin, n_seg
+        _vp, _vp, _i64,                 # long_row, long_seg_ptr, n_long
+        _vp, _vp, _vp, _i64,            # small_row, small_col, small_val, n_small
+        _vp, _i64, _vp,                 # mid_row, n_mid, partial
+        _u32, _vp]),                    # flags, stream
+    "gnn_spmm_csr_hub_bf16": (ctypes.c_int, [
+        _vp, _vp, _vp, _i64,            # rowptr, col_hub, val, n_rows
+        _vp, _i64, _vp, _i64, _i32, _i64,  # x (bf16), ldx, xh, ldh, xh_f32, feat
+        _vp, _vp, _i64,                 # bias, y, ldy
+        _i64, _vp, _vp, _i64,           # seg_len, seg_row, seg_begin, n_seg
+        _vp, _vp, _i64,                 # long_row, long_seg_ptr, n_long
+        _vp, _vp, _vp, _i64,            # small_row, small_col, small_val, n_small
+        _vp, _i64, _vp,                 # mid_row, n_mid, partial
+        _u32, _vp]),                    # flags, stream
+    "gnn_spmm_csr_tasks_bf16": (ctypes.c_int, [
+        _vp, _vp, _vp, _i64,            # rowptr, col, val, n_rows
+        _vp, _i64, _vp, _i64, _i32, _i64,  # x (bf16), ldx, xh (nullable), ldh, xh_f32, feat
+        _vp, _vp, _i64,                 # bias, y, ldy
+        _i64, _vp, _vp, _i64,           # seg_len, seg_row, seg_begin, n_seg
+        _vp, _vp, _i64,                 # long_row, long_seg_ptr, n_long
+        _vp, _i64, _vp, _i64,           # mid_row, n_mid, task_row, n_task
+        _vp, _u32, _vp]),               # partial, flags, stream
+    "gnn_gather_rows_bf16": (ctypes.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _vp]),
+    "gnn_gcn_transform_bf16out": (ctypes.c_int, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64,
+                                                 _vp]),
+    "gnn_gcn_transform_rows_bf16out": (ctypes.c_int, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64,
+                                                      _vp, _i64, _vp, _vp]),
     "gnn_spmm_tasks_check": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp]),
     "gnn_sage_gather_concat_f32": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64,
                                                    _i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp]),

@@ -51,6 +51,8 @@ struct TfEpi {
   float drop_scale = 1.f;       // 1 / (1 - p)
   uint64_t seed = 0;
   int col0 = 0;                 // column offset of this launch (the two-launch 256 split)
+  // host side only: y is a bf16 table (row stride in bf16 elements); selects the Y16 kernels
+  bool y_bf16 = false;
   TfEpi shifted(int c) const {
     TfEpi e = *this;
     if (e.bias) e.bias += c;
@@ -61,6 +63,10 @@ struct TfEpi {
 // kernel epilogue modes
 constexpr int kTfPlain = 0, kTfScatter = 1, kTfClassify = 2;
 using tf32x4 = __attribute__((ext_vector_type(4))) float;
+// column c of a y row for the two-launch splits: y counts floats, or bf16 elements (y_bf16)
+static float* y_shifted(float* y, int c, const TfEpi& epi) {
+  return epi.y_bf16 ? reinterpret_cast<float*>(reinterpret_cast<uint16_t*>(y) + c) : y + c;
+}
 // split3 / swz6 / x6_pitch (fp32 products from bf16 MFMAs): common.hpp
 
 #ifndef GNN_TF_SINGLE_BUFFER
@@ -96,7 +102,11 @@ using tf32x4 = __attribute__((ext_vector_type(4))) float;
 // GraphSAGE.py:51-52): each lane dots its 4 * CB output columns of a row with the classifier
 // weights, the 4 lane quarters are summed by shuffles and the NW waves' partials through LDS
 // (fixed order, deterministic), + bias: logits[row, c] for c < n_cls <= 4.
-template <int K, int CB, int NW, bool RELU, int TR, int MODE, bool X6 = false>
+// Y16 (gnn_gcn_transform_bf16out / _rows_bf16out; plain and scattered modes without ReLU): y is
+// a bf16 table, ldy in bf16 elements; a lane rounds its four fp32 results to bf16 (to nearest
+// even, NaN stays NaN, +-inf stays +-inf: v_cvt_pk_bf16_f32) and stores 8 B. The MFMA sequence
+// is the fp32 entry's, so what is stored is the rounding of exactly the value that entry stores.
+template <int K, int CB, int NW, bool RELU, int TR, int MODE, bool X6 = false, bool Y16 = false>
 __global__ __launch_bounds__(NW * kWave) void gcn_transform_kernel(
     const float* __restrict__ x, int64_t ldx, int64_t n_rows, const float* __restrict__ w,
     float* __restrict__ y, int64_t ldy, const int64_t* __restrict__ y_row, int64_t n_y,
@@ -367,7 +377,14 @@ __global__ __launch_bounds__(NW * kWave) void gcn_transform_kernel(
             o.z *= dropout_keep(epi.seed, orow, c + 2, epi.drop_p) ? epi.drop_scale : 0.f;
             o.w *= dropout_keep(epi.seed, orow, c + 3, epi.drop_p) ? epi.drop_scale : 0.f;
           }
-          *reinterpret_cast<float4*>(y + orow * ldy + (wv * CB + cb) * 16 + 4 * q) = o;
+          if constexpr (Y16) {
+            const bf16x4 o16 = {static_cast<__bf16>(o.x), static_cast<__bf16>(o.y),
+                                static_cast<__bf16>(o.z), static_cast<__bf16>(o.w)};
+            *reinterpret_cast<bf16x4*>(reinterpret_cast<__bf16*>(y) + orow * ldy +
+                                       (wv * CB + cb) * 16 + 4 * q) = o16;
+          } else {
+            *reinterpret_cast<float4*>(y + orow * ldy + (wv * CB + cb) * 16 + 4 * q) = o;
+          }
         }
       }
       if constexpr (CLS) {  // every lane, rows past n_rows included (their sums go unused)
@@ -444,6 +461,19 @@ template <int K, int CB, int NW, bool RELU, int TR, bool X6>
 static void launch_transform_kernel(dim3 grid, const float* x, int64_t ldx, int64_t n_rows,
                                     const float* w, float* y, int64_t ldy, const RowIdx& ri,
                                     const Classifier& cls, const TfEpi& epi, hipStream_t s) {
+  if constexpr (!RELU) {
+    if (epi.y_bf16) {  // the bf16 store epilogue: plain and scattered modes of the GCN transform
+      if (ri.row != nullptr)
+        hipLaunchKernelGGL((gcn_transform_kernel<K, CB, NW, false, TR, kTfScatter, X6, true>), grid,
+                           dim3(NW * kWave), 0, s, x, ldx, n_rows, w, y, ldy, ri.row, ri.n_y,
+                           ri.err, cls, ri.live, epi);
+      else
+        hipLaunchKernelGGL((gcn_transform_kernel<K, CB, NW, false, TR, kTfPlain, X6, true>), grid,
+                           dim3(NW * kWave), 0, s, x, ldx, n_rows, w, y, ldy, ri.row, ri.n_y,
+                           ri.err, cls, ri.live, epi);
+      return;
+    }
+  }
   if (ri.row != nullptr)  // a template flag: no index loads in the in-order kernel
     hipLaunchKernelGGL((gcn_transform_kernel<K, CB, NW, RELU, TR, kTfScatter, X6>), grid,
                        dim3(NW * kWave), 0, s, x, ldx, n_rows, w, y, ldy, ri.row, ri.n_y, ri.err,
@@ -536,8 +566,8 @@ static int dispatch_transform(int64_t fout, const float* x, int64_t ldx, int64_t
       // 1-block kernel, one per half of W's rows (X read twice; memory-bound either way)
       const int rc = dispatch_transform<K, RELU>(128, x, ldx, n_rows, w, y, ldy, ri, cls, epi, s);
       if (rc != GNN_OK) return rc;
-      return dispatch_transform<K, RELU>(128, x, ldx, n_rows, w + 128 * K, y + 128, ldy, ri, cls,
-                                        epi.shifted(128), s);
+      return dispatch_transform<K, RELU>(128, x, ldx, n_rows, w + 128 * K, y_shifted(y, 128, epi),
+                                        ldy, ri, cls, epi.shifted(128), s);
     } else if constexpr (GNN_TF_ONE256) {
       // one launch, 8 waves x 2 column blocks (128 W values per lane resident, 200 VGPRs):
       // X read and staged once for all 256 columns. In one process (tools/transform_tile_ab.py,
@@ -549,8 +579,8 @@ static int dispatch_transform(int64_t fout, const float* x, int64_t ldx, int64_t
       if (cls.logits != nullptr) return GNN_E_UNSUPPORTED;
       const int rc = dispatch_transform<K, RELU>(128, x, ldx, n_rows, w, y, ldy, ri, cls, epi, s);
       if (rc != GNN_OK) return rc;
-      return dispatch_transform<K, RELU>(128, x, ldx, n_rows, w + 128 * K, y + 128, ldy, ri, cls,
-                                        epi.shifted(128), s);
+      return dispatch_transform<K, RELU>(128, x, ldx, n_rows, w + 128 * K, y_shifted(y, 128, epi),
+                                        ldy, ri, cls, epi.shifted(128), s);
     }
   }
   return GNN_E_UNSUPPORTED;
@@ -633,6 +663,31 @@ extern "C" int gnn_gcn_transform_rows_f32(const float* x, int64_t ldx, int64_t n
   if (n_rows > 0 && n_y == 0) return GNN_E_ARG;  // every id would be out of range
   return transform_entry<false>(x, ldx, n_rows, k, w, fout, y, ldy, stream,
                                 RowIdx{y_row, n_y, err_flag});
+}
+
+// y = bf16(x w^T): the transform's output stored as bf16 [n_rows, ldy] (ldy in bf16 elements),
+// the support table of the bf16 aggregation (gnn_spmm_csr_bf16)
+extern "C" int gnn_gcn_transform_bf16out(const float* x, int64_t ldx, int64_t n_rows, int64_t k,
+                                         const float* w, int64_t fout, uint16_t* y, int64_t ldy,
+                                         void* stream) {
+  TfEpi epi;
+  epi.y_bf16 = true;
+  return transform_entry<false>(x, ldx, n_rows, k, w, fout, reinterpret_cast<float*>(y), ldy,
+                                stream, RowIdx{nullptr, 0, nullptr},
+                                Classifier{nullptr, nullptr, nullptr, 0, 0}, epi);
+}
+
+extern "C" int gnn_gcn_transform_rows_bf16out(const float* x, int64_t ldx, int64_t n_rows,
+                                              int64_t k, const float* w, int64_t fout,
+                                              uint16_t* y, int64_t ldy, const int64_t* y_row,
+                                              int64_t n_y, int32_t* err_flag, void* stream) {
+  if (n_rows > 0 && !y_row) return GNN_E_ARG;
+  if (n_rows > 0 && n_y == 0) return GNN_E_ARG;  // every id would be out of range
+  TfEpi epi;
+  epi.y_bf16 = true;
+  return transform_entry<false>(x, ldx, n_rows, k, w, fout, reinterpret_cast<float*>(y), ldy,
+                                stream, RowIdx{y_row, n_y, err_flag},
+                                Classifier{nullptr, nullptr, nullptr, 0, 0}, epi);
 }
 
 extern "C" int gnn_linear_relu_f32(const float* x, int64_t ldx, int64_t n_rows, int64_t k,

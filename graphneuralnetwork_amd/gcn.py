@@ -27,6 +27,11 @@ SpMM dS = A dY reads its hub rows in place too. In training, a layer with in_fea
 out_features runs as (A X) W^T + b (ops._GcnLayerFn), and a Graph_conv_layer -> ReLU ->
 Dropout triple of such a layer as one op: ReLU and (hashed) dropout in the transform's store
 epilogue, their backward folded into the weight-gradient pass (``_fuse_train``).
+
+Opt-in at inference: under ``ops.support_dtype(torch.bfloat16)`` (and no grad) a layer whose
+shape the MFMA transform covers keeps its support in bf16 -- written by the transform's store
+epilogue, gathered by the SpMM into fp32 sums -- so no fp32 support tensor exists; inputs,
+outputs and parameters stay fp32.
 """
 from __future__ import annotations
 
@@ -196,15 +201,21 @@ class Graph_conv_layer(nn.Module):
             y = gcn_layer(g, X_input, self.dense.weight, self.bias)
             return F.relu(y) if activation == 'relu' else y
         if X_input.is_cuda and not training:
-            order = column_order(g, self.out_features)
+            # ops.SUPPORT_DTYPE = bfloat16 (no grad only): the transform stores the support as
+            # bf16 and the SpMM gathers bf16 rows into fp32 sums; no fp32 support, no cast pass.
+            # A shape the transform does not cover (support None below) stays fp32
+            sdt = (ops.SUPPORT_DTYPE if not torch.is_grad_enabled()
+                   and X_input.dtype == torch.float32 else torch.float32)
+            esize = 2 if sdt == torch.bfloat16 else 4
+            order = column_order(g, self.out_features, esize)
             if order is not None and X_input.shape[0] == g.n_cols:
                 # support rows in the column-degree order of A P^T: the SpMM then reads its hub
                 # rows in place; A P^T (P X W^T) = A X W^T, rows in the original order
                 support = gcn_transform(X_input, self.dense.weight, out_rows=order.inv,
-                                        check_rows=False)
+                                        check_rows=False, out_dtype=sdt)
                 if support is not None:
                     return spmm_forward(order.graph, support, self.bias, activation=activation)
-            support = gcn_transform(X_input, self.dense.weight)  # MFMA kernel (inference)
+            support = gcn_transform(X_input, self.dense.weight, out_dtype=sdt)  # MFMA kernel
             if support is not None:
                 return spmm_forward(g, support, self.bias, activation=activation)
         if support is None:

@@ -33,6 +33,17 @@ def _rows_f32(x: torch.Tensor, name: str) -> torch.Tensor:
     return x
 
 
+def _rows_x(x: torch.Tensor, name: str) -> torch.Tensor:
+    """The SpMM's gathered table: fp32, or bf16-stored rows (accumulated in fp32)."""
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"{name} must be float32 or bfloat16 (got {x.dtype})")
+    if x.dim() != 2:
+        raise ValueError(f"{name} must be 2-D [rows, features]")
+    if x.stride(1) != 1:
+        x = x.contiguous()
+    return x
+
+
 # Hub staging (gnn_spmm_csr_hub_f32 / gnn_gat_csr_hub_f32): when the gathered table is
 # too large to stay in the Infinity Cache, its highest-degree rows (at most HUB_ROWS rows,
 # at most HUB_BYTES) are copied into one compact table per call. A/B on MI355X
@@ -46,10 +57,12 @@ HUB_BYTES = 64 << 20
 HUB_ROWS = 131072
 
 
-def hub_rows_for(n_cols: int, feat: int) -> int:
-    """Default number of staged hub rows for a gathered table of n_cols x feat fp32
-    (0 = no staging)."""
-    if n_cols * 4 * feat < HUB_MIN_X_BYTES:
+def hub_rows_for(n_cols: int, feat: int, elem_size: int = 4) -> int:
+    """Default number of staged hub rows for a gathered table of n_cols x feat elements of
+    ``elem_size`` bytes (4: fp32, 2: bf16; 0 = no staging). The size threshold is taken on the
+    table's real bytes; the row caps are those of fp32, so a graph's hub plans are shared
+    between the element types."""
+    if n_cols * elem_size * feat < HUB_MIN_X_BYTES:
         return 0
     return min(n_cols, HUB_ROWS, max(1, HUB_BYTES // (4 * feat)))
 
@@ -74,11 +87,19 @@ XCD_SMALL_ITEM = None
 # on a degree-ordered graph (graph.degree_order) the hub rows are X's first rows: read them
 # in place instead of copying them into a staged table (XcdHubPlan.prefix / direct)
 XCD_DIRECT = True
+# bf16 rows (spmm_forward with a bfloat16 X): whether the default policy (``xcd=None``) takes
+# the XCD-sliced direct form at all. Off: measured in one process at cfg2 on the
+# column-ordered graph (tools/spmm_bf16_ab.py), the hub rows read in
+# place by the hub-staged kernel beat the two-pass XCD form, whose second pass gathers bf16 X
+# rows and fp32 partial rows through one kernel at half the occupancy. ``xcd=True`` still
+# selects it.
+XCD_BF16 = False
 
 
-def xcd_hub_rows_for(n_cols: int, feat: int) -> int:
-    """Default hub rows of the XCD-sliced staging (0 = X too small to stage)."""
-    if n_cols * 4 * feat < HUB_MIN_X_BYTES:
+def xcd_hub_rows_for(n_cols: int, feat: int, elem_size: int = 4) -> int:
+    """Default hub rows of the XCD-sliced staging (0 = X too small to stage; ``elem_size`` as
+    in ``hub_rows_for``)."""
+    if n_cols * elem_size * feat < HUB_MIN_X_BYTES:
         return 0
     return min(n_cols, XCD_HUB_ROWS, max(64, XCD_HUB_BYTES // (4 * feat)))
 
@@ -102,16 +123,32 @@ def _task_cost(feat: int) -> int:
 
 def _tasks_ok(feat: int, *ts) -> bool:
     # every column block of the launch (<= 2048 wide) must be a vector block; one of 32 or
-    # fewer columns only with the narrow tasks
-    if not SPMM_TASKS or feat % 4 or (not SPMM_TASKS_NARROW and (feat <= 32
-                                                                  or 0 < feat % 2048 <= 32)):
+    # fewer columns only with the narrow tasks. A bf16 table's vector path holds 8 elements per
+    # lane: whole 16-B pieces per row, row pitch a multiple of 8
+    bf16 = any(t is not None and t.dtype == torch.bfloat16 for t in ts)
+    if not SPMM_TASKS or feat % (8 if bf16 else 4) or (
+            not SPMM_TASKS_NARROW and (feat <= 32 or 0 < feat % 2048 <= 32)):
         return False
-    return all(t is None or (t.data_ptr() % 16 == 0 and (t.dim() == 1 or t.stride(0) % 4 == 0))
-               for t in ts)
+    return all(t is None or (t.data_ptr() % 16 == 0 and (
+        t.dim() == 1 or t.stride(0) % (8 if t.dtype == torch.bfloat16 else 4) == 0))
+        for t in ts)
+
+
+def _xh_f32(xh) -> int:
+    """The bf16 entries' ``xh_f32`` argument: 1 for an fp32 hub table (the XCD-direct partial
+    rows), 0 for a bf16 one or none."""
+    return int(xh is not None and xh.dtype == torch.float32)
 
 
 def _spmm_tasks_call(lib, g: CsrGraph, col: torch.Tensor, tp, x, xh, feat, bias, y, ldy,
                      partial, flags, stream, what):
+    if x.dtype == torch.bfloat16:
+        _lib.check(lib.gnn_spmm_csr_tasks_bf16(
+            g.rowptr.data_ptr(), col.data_ptr(), g.val.data_ptr(), g.n_rows, x.data_ptr(),
+            x.stride(0), _lib.ptr(xh), xh.stride(0) if xh is not None else 0, _xh_f32(xh), feat,
+            _lib.ptr(bias), y.data_ptr(), ldy, tp.seg_len, *tp.args(), _lib.ptr(partial), flags,
+            stream), what.replace("_f32", "_bf16"))
+        return
     _lib.check(lib.gnn_spmm_csr_tasks_f32(
         g.rowptr.data_ptr(), col.data_ptr(), g.val.data_ptr(), g.n_rows, x.data_ptr(),
         x.stride(0), _lib.ptr(xh), xh.stride(0) if xh is not None else 0, feat, _lib.ptr(bias),
@@ -120,10 +157,35 @@ def _spmm_tasks_call(lib, g: CsrGraph, col: torch.Tensor, tp, x, xh, feat, bias,
 
 def _spmm_hub_call(lib, g: CsrGraph, col: torch.Tensor, plan, pargs, x, xh, feat, bias, y, ldy,
                    partial, flags, stream, what):
+    if x.dtype == torch.bfloat16:
+        _lib.check(lib.gnn_spmm_csr_hub_bf16(
+            g.rowptr.data_ptr(), col.data_ptr(), g.val.data_ptr(), g.n_rows, x.data_ptr(),
+            x.stride(0), xh.data_ptr(), xh.stride(0), _xh_f32(xh), feat, _lib.ptr(bias),
+            y.data_ptr(), ldy, plan.seg_len, *pargs, _lib.ptr(partial), flags, stream),
+            what.replace("_f32", "_bf16"))
+        return
     _lib.check(lib.gnn_spmm_csr_hub_f32(
         g.rowptr.data_ptr(), col.data_ptr(), g.val.data_ptr(), g.n_rows, x.data_ptr(),
         x.stride(0), xh.data_ptr(), xh.stride(0), feat, _lib.ptr(bias), y.data_ptr(), ldy,
         plan.seg_len, *pargs, _lib.ptr(partial), flags, stream), what)
+
+
+def _spmm_plain_call(lib, g: CsrGraph, plan, pargs, x, feat, bias, y, ldy, partial, flags, stream,
+                     what):
+    fn = lib.gnn_spmm_csr_bf16 if x.dtype == torch.bfloat16 else lib.gnn_spmm_csr_f32
+    _lib.check(fn(g.rowptr.data_ptr(), g.col.data_ptr(), g.val.data_ptr(), g.n_rows,
+                  x.data_ptr(), x.stride(0), feat, _lib.ptr(bias), y.data_ptr(), ldy,
+                  plan.seg_len, *pargs, _lib.ptr(partial), flags, stream),
+               what.replace("_f32", "_bf16") if x.dtype == torch.bfloat16 else what)
+
+
+def _gather_hub_rows(lib, x, hub_ids, k, feat, out, err, stream):
+    """out[:k] = x[hub_ids]: the staging copy of the hub rows (fp32 or bf16 elements)."""
+    fn, name = ((lib.gnn_gather_rows_bf16, "gnn_gather_rows_bf16")
+                if x.dtype == torch.bfloat16 else
+                (lib.gnn_gather_rows_f32, "gnn_gather_rows_f32"))
+    _lib.check(fn(x.data_ptr(), x.stride(0), x.shape[0], hub_ids.data_ptr(), k, feat,
+                  out.data_ptr(), out.stride(0), err.data_ptr(), stream), name)
 
 
 def spmm_forward(g: CsrGraph, x: torch.Tensor, bias: torch.Tensor | None = None,
@@ -145,11 +207,23 @@ def spmm_forward(g: CsrGraph, x: torch.Tensor, bias: torch.Tensor | None = None,
     ``xcd`` = XCD-sliced hub staging (``graph.XcdHubPlan``; default: on for graphs of at
     least XCD_MIN_NNZ entries whose X is staged and no explicit ``hubs``). Same sums,
     regrouped: equal to the unstaged result to fp32 rounding, bitwise reproducible.
+
+    ``x`` may be bfloat16 (feature rows stored as under ``torch.autocast``): the gathered rows
+    are widened exactly and accumulated in fp32 by the same kernels (gnn_spmm_csr_bf16 and its
+    hub / tasks forms); ``bias``, ``out`` and the result stay float32, and every option above
+    works. Two differences in routing, not in what is computed: the XCD-sliced form exists for
+    bf16 only where the hub rows are X's first rows (a degree-ordered graph, read in place);
+    elsewhere, where fp32 would stage hub and partial rows in one buffer, a bf16 ``x`` takes
+    the hub-staged non-XCD path with the same ``hubs``. And by default (``xcd=None``) a bf16
+    ``x`` takes the hub-staged path on every graph (``XCD_BF16``: it measured faster);
+    ``xcd=True`` selects the XCD-sliced direct form.
     """
     if accumulate and out is None:  # checked first: it is a usage error on any device
         raise ValueError("accumulate=True needs `out` (it adds into the caller's buffer)")
     _require_device(g.rowptr, x, bias, out)
-    x = _rows_f32(x, "X")
+    x = _rows_x(x, "X")
+    bf16 = x.dtype == torch.bfloat16
+    esize = x.element_size()
     if x.shape[0] != g.n_cols:
         raise ValueError(f"X has {x.shape[0]} rows, adjacency has {g.n_cols} columns")
     feat = x.shape[1]
@@ -165,19 +239,24 @@ def spmm_forward(g: CsrGraph, x: torch.Tensor, bias: torch.Tensor | None = None,
         return out
     seg = seg_len if seg_len is not None else seg_len_for(feat)
     if x.numel() == 0:  # no column to gather from (e.g. an empty halo): never read
-        x = torch.empty((1, feat), dtype=torch.float32, device=x.device)
+        x = torch.empty((1, feat), dtype=x.dtype, device=x.device)
     lib = _lib.load()
     flags = _ACT_FLAGS[activation] | (_lib.EPI_ACCUMULATE if accumulate else 0)
     stream = _lib.stream_handle(x.device)
     # out += A.X with no bias / activation: rows without edges stay as they are
     skip_empty = accumulate and bias is None and activation is None
     if xcd is None:
-        xcd = hubs is None and g.nnz >= XCD_MIN_NNZ and xcd_hub_rows_for(g.n_cols, feat) > 0
+        xcd = (hubs is None and g.nnz >= XCD_MIN_NNZ and (not bf16 or XCD_BF16)
+               and xcd_hub_rows_for(g.n_cols, feat, esize) > 0)
     if xcd and g.nnz:
-        kx = xcd_hub_rows_for(g.n_cols, feat) if hubs is None else min(int(hubs), g.n_cols)
+        kx = (xcd_hub_rows_for(g.n_cols, feat, esize) if hubs is None
+              else min(int(hubs), g.n_cols))
         chunk = min(XCD_CHUNK, seg)
+        ok = kx >= 8 * XCD_PHASES and chunk >= 4
+        if ok and bf16 and not (XCD_DIRECT and g.hub_plan(kx).prefix):
+            ok = False  # bf16: the direct form only (one buffer cannot hold both row types)
         xp = (g.xcd_hub_plan(kx, XCD_MIN_DEG, chunk, XCD_PHASES, XCD_ITEM_ROWS, XCD_SMALL_ITEM)
-              if kx >= 8 * XCD_PHASES and chunk >= 4 else None)
+              if ok else None)
         if xp is not None:
             _spmm_xcd(lib, g, xp, x, feat, bias, out, seg, skip_empty, flags, stream)
             return out
@@ -186,18 +265,15 @@ def spmm_forward(g: CsrGraph, x: torch.Tensor, bias: torch.Tensor | None = None,
     if plan.n_seg:
         partial = torch.empty((plan.n_seg, feat), dtype=torch.float32, device=x.device)
     pargs = plan.args(skip_empty=skip_empty)
-    k = hub_rows_for(g.n_cols, feat) if hubs is None else min(int(hubs), g.n_cols)
+    k = hub_rows_for(g.n_cols, feat, esize) if hubs is None else min(int(hubs), g.n_cols)
     tasks = _tasks_ok(feat, x, out, bias, partial)
     if k > 0 and g.nnz:
         hp = g.hub_plan(k)
         if XCD_DIRECT and hp.prefix:  # degree-ordered columns: the hub rows are X's first rows
             xh = x
         else:
-            xh = torch.empty((hp.k, feat), dtype=torch.float32, device=x.device)
-            _lib.check(lib.gnn_gather_rows_f32(x.data_ptr(), x.stride(0), x.shape[0],
-                                               hp.hub_ids.data_ptr(), hp.k, feat, xh.data_ptr(),
-                                               feat, hp.err.data_ptr(), stream),
-                       "gnn_gather_rows_f32")
+            xh = torch.empty((hp.k, feat), dtype=x.dtype, device=x.device)
+            _gather_hub_rows(lib, x, hp.hub_ids, hp.k, feat, xh, hp.err, stream)
         if tasks:
             gh = CsrGraph(g.rowptr, hp.col_hub, g.val, g.n_rows, g.n_cols)
             _spmm_tasks_call(lib, gh, hp.col_hub,
@@ -206,11 +282,8 @@ def spmm_forward(g: CsrGraph, x: torch.Tensor, bias: torch.Tensor | None = None,
                              flags | (_lib.EPI_SKIP_EMPTY if skip_empty else 0), stream,
                              "gnn_spmm_csr_tasks_f32 (hub)")
             return out
-        rc = lib.gnn_spmm_csr_hub_f32(
-            g.rowptr.data_ptr(), hp.col_hub.data_ptr(), g.val.data_ptr(), g.n_rows,
-            x.data_ptr(), x.stride(0), xh.data_ptr(), xh.stride(0), feat, _lib.ptr(bias),
-            out.data_ptr(), out.stride(0), plan.seg_len, *pargs, _lib.ptr(partial), flags, stream)
-        _lib.check(rc, "gnn_spmm_csr_hub_f32")
+        _spmm_hub_call(lib, g, hp.col_hub, plan, pargs, x, xh, feat, bias, out, out.stride(0),
+                       partial, flags, stream, "gnn_spmm_csr_hub_f32")
         return out
     if tasks and g.nnz:
         _spmm_tasks_call(lib, g, g.col, g.task_plan(seg, TASK_MAX_DEG, _task_cost(feat)), x,
@@ -219,11 +292,8 @@ def spmm_forward(g: CsrGraph, x: torch.Tensor, bias: torch.Tensor | None = None,
                          flags | (_lib.EPI_SKIP_EMPTY if skip_empty else 0), stream,
                          "gnn_spmm_csr_tasks_f32")
         return out
-    rc = lib.gnn_spmm_csr_f32(
-        g.rowptr.data_ptr(), g.col.data_ptr(), g.val.data_ptr(), g.n_rows,
-        x.data_ptr(), x.stride(0), feat, _lib.ptr(bias), out.data_ptr(), out.stride(0),
-        plan.seg_len, *pargs, _lib.ptr(partial), flags, stream)
-    _lib.check(rc, "gnn_spmm_csr_f32")
+    _spmm_plain_call(lib, g, plan, pargs, x, feat, bias, out, out.stride(0), partial, flags,
+                     stream, "gnn_spmm_csr_f32")
     return out
 
 
@@ -263,6 +333,30 @@ def _spmm_xcd(lib, g: CsrGraph, xp, x, feat, bias, out, seg, skip_empty, flags, 
                    "gnn_spmm_csr_hub_f32 (xcd rest)")
 
 
+# Storage type of the support tensor S = X W^T between Graph_conv_layer's transform and its
+# aggregation at inference. torch.bfloat16: the transform stores S as bf16
+# (gnn_gcn_transform_bf16out) and the SpMM gathers bf16 rows, accumulating in fp32
+# (gnn_spmm_csr_bf16): half the bytes per gathered row and half the support's memory, for a
+# relative rounding of 2^-9 per support element. Training, and layers whose shape the MFMA
+# transform does not cover, stay fp32. Set it through ``support_dtype``.
+SUPPORT_DTYPE = torch.float32
+
+
+@contextlib.contextmanager
+def support_dtype(dtype: torch.dtype):
+    """Sets ``SUPPORT_DTYPE`` (torch.float32 or torch.bfloat16) for the block and restores the
+    previous value on exit (nests)."""
+    global SUPPORT_DTYPE
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"support dtype must be float32 or bfloat16 (got {dtype})")
+    prev = SUPPORT_DTYPE
+    SUPPORT_DTYPE = dtype
+    try:
+        yield
+    finally:
+        SUPPORT_DTYPE = prev
+
+
 # Graph_conv_layer runs its aggregation over the column-degree-ordered graph A P^T
 # (graph.degree_order(rows=False)) whenever the SpMM would take the XCD-sliced path: the
 # transform writes the support rows in that order (gcn_transform rows=perm) and the SpMM reads
@@ -289,12 +383,12 @@ def _cached_column_order(g: CsrGraph):
     return o
 
 
-def column_order(g: CsrGraph, feat: int):
-    """The cached ``DegreeOrder(rows=False)`` of ``g`` when a feat-wide SpMM over it would
-    take the XCD-sliced hub path (else None)."""
+def column_order(g: CsrGraph, feat: int, elem_size: int = 4):
+    """The cached ``DegreeOrder(rows=False)`` of ``g`` when a feat-wide SpMM over it (rows of
+    ``elem_size``-byte elements) would take the XCD-sliced hub path (else None)."""
     if not (DEGREE_ORDER and XCD_DIRECT) or g.nnz < XCD_MIN_NNZ or g._plans.get("_degree_ordered"):
         return None
-    if xcd_hub_rows_for(g.n_cols, feat) < 8 * XCD_PHASES:
+    if xcd_hub_rows_for(g.n_cols, feat, elem_size) < 8 * XCD_PHASES:
         return None
     return _cached_column_order(g)
 
@@ -481,16 +575,15 @@ def _spmm_xcd_direct(lib, xp, x, feat, bias, out, seg, skip_empty, flags, stream
     """The XCD-sliced SpMM of a degree-ordered graph (graph.degree_order): the hub rows are
     X's first k rows, so there is no staging copy. Pass 1 (plain kernel) reads the items'
     hub rows from X into a partial-row buffer; pass 2 reads X and that buffer (c < 0 ->
-    partial row -1-c)."""
+    partial row -1-c). The partial rows are fp32 for a bf16 X too (the bf16 hub / tasks
+    entries with an fp32 xh)."""
     items, rest = xp.direct()
     part = torch.empty((xp.n_pos, feat), dtype=torch.float32, device=x.device)
     p1 = items.plan(seg)
     if p1.n_seg or p1.n_small:
         raise RuntimeError("XCD hub plan: item rows outside the mid-row class")
-    _lib.check(lib.gnn_spmm_csr_f32(
-        items.rowptr.data_ptr(), items.col.data_ptr(), items.val.data_ptr(), items.n_rows,
-        x.data_ptr(), x.stride(0), feat, None, part.data_ptr(), feat, p1.seg_len, *p1.args(),
-        None, 0, stream), "gnn_spmm_csr_f32 (xcd direct items)")
+    _spmm_plain_call(lib, items, p1, p1.args(), x, feat, None, part, feat, None, 0, stream,
+                     "gnn_spmm_csr_f32 (xcd direct items)")
     if _tasks_ok(feat, x, out, bias, part):
         tp = rest.task_plan(seg, TASK_MAX_DEG, _task_cost(feat))
         partial = None
@@ -504,11 +597,9 @@ def _spmm_xcd_direct(lib, xp, x, feat, bias, out, seg, skip_empty, flags, stream
     partial = None
     if p2.n_seg:
         partial = torch.empty((p2.n_seg, feat), dtype=torch.float32, device=x.device)
-    _lib.check(lib.gnn_spmm_csr_hub_f32(
-        rest.rowptr.data_ptr(), rest.col.data_ptr(), rest.val.data_ptr(), rest.n_rows,
-        x.data_ptr(), x.stride(0), part.data_ptr(), feat, feat, _lib.ptr(bias), out.data_ptr(),
-        out.stride(0), p2.seg_len, *p2.args(skip_empty=skip_empty), _lib.ptr(partial), flags,
-        stream), "gnn_spmm_csr_hub_f32 (xcd direct rest)")
+    _spmm_hub_call(lib, rest, rest.col, p2, p2.args(skip_empty=skip_empty), x, part, feat, bias,
+                   out, out.stride(0), partial, flags, stream,
+                   "gnn_spmm_csr_hub_f32 (xcd direct rest)")
 
 
 class _SpmmFn(torch.autograd.Function):
@@ -530,7 +621,11 @@ class _SpmmFn(torch.autograd.Function):
 
 
 def spmm(g: CsrGraph, x: torch.Tensor, bias: torch.Tensor | None = None) -> torch.Tensor:
-    """Differentiable (w.r.t. X and bias) CSR SpMM on the device."""
+    """Differentiable (w.r.t. X and bias) CSR SpMM on the device. bf16 rows are an inference
+    storage type (``spmm_forward``): a bf16 tensor that requires grad raises TypeError."""
+    if torch.is_grad_enabled() and x.dtype == torch.bfloat16 and x.requires_grad:
+        raise TypeError("spmm: bfloat16 X is supported at inference only; training runs in "
+                        "fp32 (gradients flow through float32 feature rows)")
     if torch.is_grad_enabled() and (x.requires_grad or (bias is not None and bias.requires_grad)):
         return _SpmmFn.apply(x, bias, g)
     return spmm_forward(g, x, bias)
@@ -981,7 +1076,7 @@ def gcn_transform(x: torch.Tensor, weight: torch.Tensor, relu: bool = False,
                   out: torch.Tensor | None = None, out_rows: torch.Tensor | None = None,
                   check_rows: bool = True, live: torch.Tensor | None = None,
                   bias: torch.Tensor | None = None, dropout_p: float = 0.0,
-                  seed: int = 0) -> torch.Tensor | None:
+                  seed: int = 0, out_dtype: torch.dtype = torch.float32) -> torch.Tensor | None:
     """support = x @ weight^T on fp32 MFMA (gnn_gcn_transform_f32), the dense half of
     Graph_conv_layer.forward (GCN/GCN.py:42); ``relu=True``: max(x @ weight^T, 0)
     (gnn_linear_relu_f32, the SageLayer at GraphSAGE/GraphSAGE.py:18-20). Inference only
@@ -1002,8 +1097,18 @@ def gcn_transform(x: torch.Tensor, weight: torch.Tensor, relu: bool = False,
     ``bias`` (fp32 [fout]) and ``dropout_p`` / ``seed`` (without out_rows / live):
     dropout(act(x @ weight^T + bias)) in the store epilogue (gnn_gcn_transform_epi_f32; act =
     ReLU if ``relu``; element (i, c) kept iff the (seed, i, c) hash clears p, kept values scaled
-    by 1 / (1 - p))."""
+    by 1 / (1 - p)).
+
+    ``out_dtype=torch.bfloat16`` (or a bfloat16 ``out``, whose dtype decides): the result is
+    stored as bf16 by the kernel's store epilogue (gnn_gcn_transform_bf16out /
+    _rows_bf16out; round to nearest even of exactly the fp32 value, NaN and +-inf kept) --
+    the plain and ``out_rows`` forms only (no relu / live / bias / dropout)."""
     _require_device(x, weight)
+    if out is not None:
+        out_dtype = out.dtype
+    if out_dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"gcn_transform stores float32 or bfloat16 (got {out_dtype})")
+    y16 = out_dtype == torch.bfloat16
     if (x.dtype != torch.float32 or weight.dtype != torch.float32 or x.dim() != 2
             or weight.dim() != 2 or x.shape[1] != weight.shape[1]):
         return None
@@ -1016,6 +1121,8 @@ def gcn_transform(x: torch.Tensor, weight: torch.Tensor, relu: bool = False,
     if out_rows is not None and relu:
         raise ValueError("out_rows= is supported without the ReLU epilogue only")
     epi = bias is not None or dropout_p > 0
+    if y16 and (relu or epi or live is not None):
+        raise ValueError("a bfloat16 result is supported without relu / live / bias / dropout")
     if epi and (out_rows is not None or live is not None):
         raise ValueError("bias= / dropout_p= are supported without out_rows / live only")
     if not 0.0 <= dropout_p < 1.0:
@@ -1038,11 +1145,10 @@ def gcn_transform(x: torch.Tensor, weight: torch.Tensor, relu: bool = False,
     w = weight.contiguous()
     m = x.shape[0]
     if out is None:
-        out = torch.empty((m, fout), dtype=torch.float32, device=x.device)
+        out = torch.empty((m, fout), dtype=out_dtype, device=x.device)
     elif (out.dim() != 2 or out.shape[1] != fout or (out_rows is None and out.shape[0] != m)
-          or out.dtype != torch.float32 or out.stride(1) != 1
-          or out.stride(0) % 4 or out.data_ptr() % 16):
-        raise ValueError("out must be float32 [rows, fout], 16-B aligned rows")
+          or out.stride(1) != 1 or out.stride(0) % 4 or out.data_ptr() % 16):
+        raise ValueError("out must be float32 or bfloat16 [rows, fout], 16-B aligned rows")
     if out_rows is not None:
         _require_device(out_rows)
         if out_rows.dtype != torch.int64 or out_rows.dim() != 1 or out_rows.numel() != m:
@@ -1051,10 +1157,12 @@ def gcn_transform(x: torch.Tensor, weight: torch.Tensor, relu: bool = False,
         if m == 0:
             return out
         err = torch.zeros(1, dtype=torch.int32, device=x.device)
-        _lib.check(lib.gnn_gcn_transform_rows_f32(
+        fn, name = ((lib.gnn_gcn_transform_rows_bf16out, "gnn_gcn_transform_rows_bf16out")
+                    if y16 else (lib.gnn_gcn_transform_rows_f32, "gnn_gcn_transform_rows_f32"))
+        _lib.check(fn(
             x.data_ptr(), x.stride(0), m, k, w.data_ptr(), fout, out.data_ptr(), out.stride(0),
             out_rows.data_ptr(), out.shape[0], err.data_ptr(), _lib.stream_handle(x.device)),
-            "gnn_gcn_transform_rows_f32")
+            name)
         if check_rows and int(err.item()):
             raise IndexError("gcn_transform: an output row id is out of range")
         return out
@@ -1071,6 +1179,7 @@ def gcn_transform(x: torch.Tensor, weight: torch.Tensor, relu: bool = False,
             out.stride(0), _lib.stream_handle(x.device)), "gnn_gcn_transform_epi_f32")
         return out
     fn, name = ((lib.gnn_linear_relu_f32, "gnn_linear_relu_f32") if relu else
+                (lib.gnn_gcn_transform_bf16out, "gnn_gcn_transform_bf16out") if y16 else
                 (lib.gnn_gcn_transform_f32, "gnn_gcn_transform_f32"))
     _lib.check(fn(x.data_ptr(), x.stride(0), x.shape[0], k, w.data_ptr(), fout, out.data_ptr(),
                   out.stride(0), _lib.stream_handle(x.device)), name)

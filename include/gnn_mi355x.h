@@ -142,6 +142,61 @@ int gnn_spmm_csr_tasks_f32(const int64_t* rowptr, const int32_t* col, const floa
                            uint32_t flags, void* stream);
 
 /*
+ * The same aggregation (GCN/GCN.py:43-45) over bf16-stored feature rows: x is a bf16 table
+ * [n_cols, ldx] (ldx in bf16 elements), everything else -- val, bias, y, partial, the
+ * accumulators and the epilogue flags -- fp32, arguments and plan as gnn_spmm_csr_f32. A bf16
+ * value is the high half of an fp32 and widens exactly, so the result is the fp32 entry's on
+ * the same values up to the grouping of the slot sums; no float atomics, fixed reduction
+ * orders: bitwise reproducible. Vector path (16-B loads, 8 bf16 per lane): feat % 8 == 0,
+ * x 16-B aligned, ldx % 8 == 0 and y / bias / partial 16-B aligned with ldy % 4 == 0; any
+ * other width, alignment (2-B) or pitch runs one element per lane. Same argument checks and
+ * return codes as gnn_spmm_csr_f32.
+ */
+int gnn_spmm_csr_bf16(const int64_t* rowptr, const int32_t* col, const float* val, int64_t n_rows,
+                      const uint16_t* x, int64_t ldx, int64_t feat, const float* bias, float* y,
+                      int64_t ldy, int64_t seg_len, const int32_t* seg_row,
+                      const int64_t* seg_begin, int64_t n_seg, const int32_t* long_row,
+                      const int32_t* long_seg_ptr, int64_t n_long, const int32_t* small_row,
+                      const int32_t* small_col, const float* small_val, int64_t n_small,
+                      const int32_t* mid_row, int64_t n_mid, float* partial, uint32_t flags,
+                      void* stream);
+
+/*
+ * gnn_spmm_csr_hub_f32 over a bf16 x (same call site, GCN/GCN.py:43-45). The hub table xh
+ * [K, ldh] has its own element type: xh_f32 == 0: bf16 rows (gnn_gather_rows_bf16 with the hub
+ * id list, or x itself when the hub columns are x's first rows), ldh in bf16 elements;
+ * xh_f32 == 1: fp32 rows, ldh in floats (pass 2 of the XCD-sliced form over a degree-ordered
+ * graph, where xh holds pass 1's fp32 partial rows); another value: GNN_E_ARG. The vector path
+ * also needs xh 16-B aligned and ldh % 8 == 0 (bf16) or % 4 == 0 (fp32). Everything else as
+ * gnn_spmm_csr_bf16 / gnn_spmm_csr_hub_f32.
+ */
+int gnn_spmm_csr_hub_bf16(const int64_t* rowptr, const int32_t* col_hub, const float* val,
+                          int64_t n_rows, const uint16_t* x, int64_t ldx, const void* xh,
+                          int64_t ldh, int32_t xh_f32, int64_t feat, const float* bias, float* y,
+                          int64_t ldy, int64_t seg_len, const int32_t* seg_row,
+                          const int64_t* seg_begin, int64_t n_seg, const int32_t* long_row,
+                          const int32_t* long_seg_ptr, int64_t n_long, const int32_t* small_row,
+                          const int32_t* small_col, const float* small_val, int64_t n_small,
+                          const int32_t* mid_row, int64_t n_mid, float* partial, uint32_t flags,
+                          void* stream);
+
+/*
+ * gnn_spmm_csr_tasks_f32 over a bf16 x (same call site, GCN/GCN.py:43-45); xh / ldh / xh_f32:
+ * the optional hub table as in gnn_spmm_csr_hub_bf16 (NULL: none). Needs the bf16 vector path
+ * (feat % 8 == 0, 16-B aligned x / xh / y / bias / partial, ldx % 8 == 0, ldh % 8 == 0 for a
+ * bf16 xh and % 4 == 0 for an fp32 one, ldy % 4 == 0), else GNN_E_UNSUPPORTED. Task contract,
+ * flags and determinism as gnn_spmm_csr_tasks_f32.
+ */
+int gnn_spmm_csr_tasks_bf16(const int64_t* rowptr, const int32_t* col, const float* val,
+                            int64_t n_rows, const uint16_t* x, int64_t ldx, const void* xh,
+                            int64_t ldh, int32_t xh_f32, int64_t feat, const float* bias, float* y,
+                            int64_t ldy, int64_t seg_len, const int32_t* seg_row,
+                            const int64_t* seg_begin, int64_t n_seg, const int32_t* long_row,
+                            const int32_t* long_seg_ptr, int64_t n_long, const int32_t* mid_row,
+                            int64_t n_mid, const int32_t* task_row, int64_t n_task, float* partial,
+                            uint32_t flags, void* stream);
+
+/*
  * Validates a task list of gnn_spmm_csr_tasks_f32 on the device: *err (device int32, zeroed by
  * the caller) gets bit 1 for a task with no row, more than 63 rows or rows outside
  * [0, n_rows), bit 2 for a task that starts before the previous one ends (tasks must be
@@ -375,6 +430,25 @@ int gnn_gcn_transform_rows_f32(const float* x, int64_t ldx, int64_t n_rows, int6
                                const float* w, int64_t fout, float* y, int64_t ldy,
                                const int64_t* y_row, int64_t n_y, int32_t* err_flag,
                                void* stream);
+
+/*
+ * gnn_gcn_transform_f32 / gnn_gcn_transform_rows_f32 with the result stored as bf16: y is a
+ * bf16 table [n_rows (or n_y), ldy], ldy in bf16 elements. The support of GCN/GCN.py:42 in
+ * the storage type the bf16 aggregation (gnn_spmm_csr_bf16) gathers, written by the transform
+ * itself: no fp32 support and no cast pass. Each lane rounds its four fp32 accumulators to
+ * bf16 -- to nearest even, NaN stays NaN, +-inf stays +-inf -- and stores 8 B; the MFMA
+ * sequence (both modes of gnn_transform_set_precision) is the fp32 entry's, so the stored
+ * value is the rounding of exactly the value that entry stores. Shapes as
+ * gnn_gcn_transform_supported (else GNN_E_UNSUPPORTED); x, w, y 16-B aligned, ldx and ldy
+ * multiples of 4 (else GNN_E_ALIGN); row ids, err_flag and GNN_E_ARG cases as the fp32 entries.
+ */
+int gnn_gcn_transform_bf16out(const float* x, int64_t ldx, int64_t n_rows, int64_t k,
+                              const float* w, int64_t fout, uint16_t* y, int64_t ldy,
+                              void* stream);
+int gnn_gcn_transform_rows_bf16out(const float* x, int64_t ldx, int64_t n_rows, int64_t k,
+                                   const float* w, int64_t fout, uint16_t* y, int64_t ldy,
+                                   const int64_t* y_row, int64_t n_y, int32_t* err_flag,
+                                   void* stream);
 
 /*
  * Feature row normalisation, bit-exact with the reference loader: normalize_features
@@ -786,6 +860,17 @@ int gnn_sage_layer_f32(const float* table, int64_t ldt, int64_t n_table, const f
  */
 int gnn_gather_rows_f32(const float* x, int64_t ldx, int64_t n_x, const int64_t* idx, int64_t n,
                         int64_t feat, float* out, int64_t ldo, int32_t* err_flag, void* stream);
+
+/*
+ * The same row gather for 2-byte elements: out[i, :feat] = x[idx[i], :feat] over a bf16 table
+ * (ldx, ldo in bf16 elements) -- the staging copy of hub rows into the compact bf16 table of
+ * gnn_spmm_csr_hub_bf16 / gnn_spmm_csr_tasks_bf16. 16-B pieces per lane when feat, ldx, ldo
+ * are multiples of 8 and x, out 16-B aligned, single elements otherwise. Out-of-range index
+ * -> *err_flag |= 1, row skipped.
+ */
+int gnn_gather_rows_bf16(const uint16_t* x, int64_t ldx, int64_t n_x, const int64_t* idx,
+                         int64_t n, int64_t feat, uint16_t* out, int64_t ldo, int32_t* err_flag,
+                         void* stream);
 
 /*
  * Hashed element dropout fused with a row gather, replacing F.dropout(x, p, training) at
