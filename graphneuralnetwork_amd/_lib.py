@@ -93,6 +93,18 @@ SIGNATURES: dict[str, tuple] = {
     "gnn_sage_gather_concat_live_f32": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp,
                                                         _i64, _i64, _i32, _vp, _i64, _vp, _i64,
                                                         _vp, _vp]),
+    # the SAGE entries over a bf16 table: the argument lists of their _f32 twins
+    "gnn_sage_aggregate_bf16": (ctypes.c_int, [_vp, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _i64,
+                                               _vp]),
+    "gnn_sage_gather_aggregate_bf16": (ctypes.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _i64,
+                                                      _i32, _vp, _i64, _vp, _vp]),
+    "gnn_sage_gather_concat_bf16": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64,
+                                                    _i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "gnn_sage_gather_concat_live_bf16": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _i64,
+                                                         _vp, _i64, _i64, _i32, _vp, _i64, _vp,
+                                                         _i64, _vp, _vp]),
+    "gnn_gather_rows_bf16_f32": (ctypes.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _vp,
+                                                _vp]),
     "gnn_halo_alltoallv_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
     "gnn_halo_rccl_path": (ctypes.c_int, [ctypes.c_char_p, _i64]),
     "gnn_spmm_plan_scratch_bytes": (_i64, [_i64]),

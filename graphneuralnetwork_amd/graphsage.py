@@ -24,8 +24,9 @@ import torch.nn.functional as F
 from torch import nn
 
 from .graph import from_coo
-from .ops import (gather_rows, gcn_transform, linear_relu_classify, sage_aggregate,
-                  sage_gather_aggregate, sage_gather_concat, sage_layer, spmm_forward)
+from .ops import (_bf16_inference_only, gather_rows, gcn_transform, linear_relu_classify,
+                  sage_aggregate, sage_gather_aggregate, sage_gather_concat, sage_layer,
+                  spmm_forward)
 
 # the inference SageLayer GEMM relu([self | agg] @ W^T) runs on the hand-written MFMA kernel
 # (gnn_linear_relu_f32). With the split-bf16 arithmetic (the default, ops.set_transform_precision)
@@ -194,6 +195,7 @@ def Aggregator(neigh_feat, agg_func='MEAN'):
 
 
 def _gather_aggregate(table, idx, agg_func, trusted=False):
+    _bf16_inference_only(table, "GraphSAGE aggregation")  # no gradient w.r.t. a bf16 table
     if agg_func in ('MEAN', 'SUM') and torch.is_grad_enabled() and table.requires_grad:
         return _GatherMeanAgg.apply(table, idx, agg_func, not trusted)
     if agg_func == 'MAXPOOL' and torch.is_grad_enabled() and table.requires_grad:
@@ -206,6 +208,7 @@ def reduce_neighbors(neigh_feat, kind='MEAN'):
     ``Gathered`` (table, [M, k] index), with autograd for MEAN / SUM / MAXPOOL."""
     if isinstance(neigh_feat, Gathered):
         return _gather_aggregate(neigh_feat.table, neigh_feat.index, kind, neigh_feat.trusted)
+    _bf16_inference_only(neigh_feat, "GraphSAGE aggregation")
     if kind in ('MEAN', 'SUM') and torch.is_grad_enabled() and neigh_feat.requires_grad:
         return _MeanAgg.apply(neigh_feat, kind)
     if kind == 'MAXPOOL' and torch.is_grad_enabled() and neigh_feat.requires_grad:
@@ -214,6 +217,7 @@ def reduce_neighbors(neigh_feat, kind='MEAN'):
 
 
 def _gather(x, idx, trusted=False):
+    _bf16_inference_only(x, "GraphSAGE row gather")
     if torch.is_grad_enabled() and x.requires_grad:
         return _GatherRows.apply(x, idx, not trusted)
     return gather_rows(x, idx, check=not trusted)
@@ -250,6 +254,10 @@ class SageLayer(nn.Module):
 def _fused_sage_layer(block, center, neigh: Gathered, dense: nn.Linear | None = None,
                       agg: str = 'MEAN'):
     """Inference SageLayer on a (table, index map) aggregate.
+
+    The table may hold the input features as bfloat16 (``neigh.table.dtype``): the gathers
+    read 2-byte elements and write the float32 [self | agg] buffer (the centre rows widened,
+    the aggregate reduced in fp32), so the GEMM and everything after it are unchanged.
 
     ``agg`` 'MAX' / 'MAXPOOL' (centre and neighbours Gathered from one table): the concat
     launch writes the argmax index as fp32 (the value torch.cat([self, argmax]) promotes it
@@ -307,7 +315,7 @@ def _fused_sage_layer(block, center, neigh: Gathered, dense: nn.Linear | None = 
         if isinstance(center, Gathered):
             gather_rows(center.table, center.index, out=buf[:, :n], check=not center.trusted)
         else:
-            buf[:, :n].copy_(center)
+            buf[:, :n].copy_(center)  # (widens a bfloat16 centre tensor)
         sage_gather_aggregate(neigh.table, neigh.index, "MEAN", check=not neigh.trusted,
                               out=buf[:, n:])
     W = block.weight.weight
@@ -353,8 +361,10 @@ class GraphSAGE(nn.Module):
         if self.agg_func == 'MEAN':
             return True
         # MAX / MAXPOOL: the one-launch concat form (centre and neighbours from one table)
+        # (a float32 table, or the stored input features as bfloat16: both halves stay fp32)
         return (self.agg_func in ('MAX', 'MAXPOOL') and isinstance(center, Gathered)
-                and center.table is neigh.table and neigh.table.dtype == torch.float32)
+                and center.table is neigh.table
+                and neigh.table.dtype in (torch.float32, torch.bfloat16))
 
     def forward(self, center_feats_data, center_nodes_map, center_neigh_feats_data, center_neigh_nodes_map,
                 contexts_negatives_feats_data, contexts_negatives_nodes_map, contexts_negatives_neigh_feats_data,

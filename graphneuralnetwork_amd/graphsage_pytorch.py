@@ -14,7 +14,8 @@ keys (``gcn.{l}.weight``, ``gcn.{l}.aggregator.weight`` / ``.bias``).
 * ``GraphSage.forward`` takes the reference's list of per-hop feature tensors;
   any hop may instead be a ``Gathered(table, ids)`` (see ``multihop_sampling``),
   in which case the hop's neighbour rows are reduced straight from the table
-  (fused gather + reduction) and never materialised.
+  (fused gather + reduction) and never materialised. The table may be bfloat16 (the stored
+  input features): the reductions run in fp32 and the hop's own rows are gathered widened.
 """
 from __future__ import annotations
 
@@ -24,6 +25,7 @@ from torch import nn
 
 from .graph import CsrGraph
 from .graphsage import Gathered, _gather, reduce_neighbors
+from .ops import gather_rows
 
 _KINDS = {"mean": "MEAN", "sum": "SUM"}
 
@@ -36,8 +38,16 @@ def _nbr_view(feat, n_src: int, k: int):
 
 
 def _rows(feat):
-    """A hop's feature rows as a tensor (row gather for a Gathered hop)."""
-    return _gather(feat.table, feat.index.reshape(-1), feat.trusted) if isinstance(feat, Gathered) else feat
+    """A hop's feature rows as a float32 tensor (row gather for a Gathered hop; a bfloat16
+    table's rows are widened by the gather itself, gnn_gather_rows_bf16_f32)."""
+    if not isinstance(feat, Gathered):
+        return feat
+    if feat.table.dtype == torch.bfloat16:
+        idx = feat.index.reshape(-1)
+        out = torch.empty((idx.numel(), feat.table.shape[1]), dtype=torch.float32,
+                          device=feat.table.device)
+        return gather_rows(feat.table, idx, out=out, check=not feat.trusted)
+    return _gather(feat.table, feat.index.reshape(-1), feat.trusted)
 
 
 def _len(feat) -> int:

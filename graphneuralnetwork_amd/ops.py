@@ -44,6 +44,24 @@ def _rows_x(x: torch.Tensor, name: str) -> torch.Tensor:
     return x
 
 
+def _bf16(t: torch.Tensor) -> bool:
+    return t.dtype == torch.bfloat16
+
+
+def _f32_or_bf16(t: torch.Tensor, name: str) -> None:
+    """The dtype rule of the SAGE ops, applied before anything else looks at the tensor."""
+    if t.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"{name} must be float32 or bfloat16 (got {t.dtype})")
+
+
+def _bf16_inference_only(t: torch.Tensor, what: str) -> None:
+    """bf16 rows are a storage type of the inputs: nothing differentiates with respect to them
+    (a bf16 table WITHOUT grad works in training -- the gradients go to the weights)."""
+    if torch.is_grad_enabled() and t.dtype == torch.bfloat16 and t.requires_grad:
+        raise TypeError(f"{what}: a bfloat16 table is supported at inference only; training "
+                        "runs in fp32 (gradients flow through float32 feature rows)")
+
+
 # Hub staging (gnn_spmm_csr_hub_f32 / gnn_gat_csr_hub_f32): when the gathered table is
 # too large to stay in the Infinity Cache, its highest-degree rows (at most HUB_ROWS rows,
 # at most HUB_BYTES) are copied into one compact table per call. A/B on MI355X
@@ -1536,12 +1554,16 @@ def _sage_out(M, F, mode, dev):
 
 def sage_aggregate(neigh: torch.Tensor, agg_func: str = "MEAN") -> torch.Tensor:
     """Aggregator over a pre-gathered [M, k, F] tensor (GraphSAGE/graph_utils.py:4-11);
-    'SUM' is NeighborAggregator's sum (GraphSAGE_Pytorch/models/Aggregator.py:21-22)."""
+    'SUM' is NeighborAggregator's sum (GraphSAGE_Pytorch/models/Aggregator.py:21-22).
+    ``neigh`` may be bfloat16 (gnn_sage_aggregate_bf16): the elements are widened exactly, the
+    sums are fp32 and the result is fp32 (int64 for 'MAX') as for a float32 tensor."""
     if agg_func not in SAGE_KINDS:
         raise RuntimeError(f"unknown agg_func {agg_func!r}")
+    _f32_or_bf16(neigh, "neigh_feat")
     _require_device(neigh)
-    if neigh.dtype != torch.float32 or neigh.dim() != 3:
-        raise TypeError("neigh_feat must be float32 [M, k, F]")
+    if neigh.dim() != 3:
+        raise TypeError("neigh_feat must be float32 or bfloat16 [M, k, F]")
+    _bf16_inference_only(neigh, "sage_aggregate")
     if neigh.stride(2) != 1:
         neigh = neigh.contiguous()
     M, k, F = neigh.shape
@@ -1551,10 +1573,10 @@ def sage_aggregate(neigh: torch.Tensor, agg_func: str = "MEAN") -> torch.Tensor:
         return torch.full((M, F), _EMPTY_FILL[mode], device=neigh.device)
     out = _sage_out(M, F, mode, neigh.device)
     lib = _lib.load()
-    _lib.check(lib.gnn_sage_aggregate_f32(neigh.data_ptr(), neigh.stride(1), neigh.stride(0), M, k,
-                                          F, mode, out.data_ptr(), F,
-                                          _lib.stream_handle(neigh.device)),
-               "gnn_sage_aggregate_f32")
+    fn, name = ((lib.gnn_sage_aggregate_bf16, "gnn_sage_aggregate_bf16") if _bf16(neigh) else
+                (lib.gnn_sage_aggregate_f32, "gnn_sage_aggregate_f32"))
+    _lib.check(fn(neigh.data_ptr(), neigh.stride(1), neigh.stride(0), M, k, F, mode,
+                  out.data_ptr(), F, _lib.stream_handle(neigh.device)), name)
     return out
 
 
@@ -1589,11 +1611,16 @@ def _sage_dst(out, M, F, mode, dev):
 
 def sage_gather_aggregate(table: torch.Tensor, idx: torch.Tensor, agg_func: str = "MEAN",
                           check: bool = True, out: torch.Tensor | None = None) -> torch.Tensor:
-    """Aggregator(torch.embedding(table, idx)) fused: [M, k] int64 indices into table [n, F]."""
+    """Aggregator(torch.embedding(table, idx)) fused: [M, k] int64 indices into table [n, F].
+    A bfloat16 ``table`` (the stored input features; gnn_sage_gather_aggregate_bf16) is read
+    at 2 bytes per element, widened exactly and reduced in fp32: the result is fp32 (int64 for
+    'MAX'), and 'MAX' / 'MAXPOOL' are exact functions of the stored values."""
     if agg_func not in SAGE_KINDS:
         raise RuntimeError(f"unknown agg_func {agg_func!r}")
+    _f32_or_bf16(table, "table")
     _require_device(table, idx)
-    table = _rows_f32(table, "table")
+    table = _rows_x(table, "table")
+    _bf16_inference_only(table, "sage_gather_aggregate")
     if idx.dim() != 2:
         raise ValueError("idx must be [M, k]")
     idx = idx.to(torch.int64)
@@ -1608,10 +1635,13 @@ def sage_gather_aggregate(table: torch.Tensor, idx: torch.Tensor, agg_func: str 
         return out.fill_(_EMPTY_FILL[mode])
     err = _err_flag(table.device, check)
     lib = _lib.load()
-    _lib.check(lib.gnn_sage_gather_aggregate_f32(
+    fn, name = ((lib.gnn_sage_gather_aggregate_bf16, "gnn_sage_gather_aggregate_bf16")
+                if _bf16(table) else
+                (lib.gnn_sage_gather_aggregate_f32, "gnn_sage_gather_aggregate_f32"))
+    _lib.check(fn(
         table.data_ptr(), table.stride(0), table.shape[0], idx.data_ptr(), idx.stride(0), M, k, F,
         mode, out.data_ptr(), out.stride(0), err.data_ptr(), _lib.stream_handle(table.device)),
-        "gnn_sage_gather_aggregate_f32")
+        name)
     if check:
         _check_err(err, "sage_gather_aggregate")
     return out
@@ -1627,12 +1657,16 @@ def sage_gather_concat(table: torch.Tensor, self_idx: torch.Tensor, idx: torch.T
     ``live``: a device int64 scalar; rows [0, min(live, M)) only (gnn_sage_gather_concat_live_f32,
     M = the capacity of a sampled batch whose frontier size the host never read).
     'MAX' (torch.argmax over the neighbours, graph_utils.py:8): the index written as fp32, the
-    value torch.cat([self, argmax]) promotes it to (GNN_SAGE_ARGMAX_F32)."""
+    value torch.cat([self, argmax]) promotes it to (GNN_SAGE_ARGMAX_F32).
+    A bfloat16 ``table`` (gnn_sage_gather_concat_live_bf16): both halves stay float32 -- the
+    centre rows are stored widened, the aggregate is reduced in fp32."""
     if agg_func not in ("MEAN", "SUM", "MAXPOOL", "MAX"):
         raise RuntimeError(f"agg_func {agg_func!r} has no concat form")
     mode = 4 if agg_func == "MAX" else SAGE_KINDS[agg_func]
+    _f32_or_bf16(table, "table")
     _require_device(table, self_idx, idx, out)
-    table = _rows_f32(table, "table")
+    table = _rows_x(table, "table")
+    _bf16_inference_only(table, "sage_gather_concat")
     if idx.dim() != 2:
         raise ValueError("idx must be [M, k]")
     idx = idx.to(torch.int64)
@@ -1651,7 +1685,7 @@ def sage_gather_concat(table: torch.Tensor, self_idx: torch.Tensor, idx: torch.T
         return out
     if k == 0:
         _empty_reduction(SAGE_KINDS[agg_func])
-        out[:, :F].copy_(gather_rows(table, self_idx, check=check))
+        gather_rows(table, self_idx, out=out[:, :F], check=check)
         out[:, F:].fill_(_EMPTY_FILL[SAGE_KINDS[agg_func]])
         return out
     if live is not None:
@@ -1660,11 +1694,14 @@ def sage_gather_concat(table: torch.Tensor, self_idx: torch.Tensor, idx: torch.T
             raise TypeError("live must be a one-element int64 device tensor")
     err = _err_flag(table.device, check)
     lib = _lib.load()
-    _lib.check(lib.gnn_sage_gather_concat_live_f32(
+    fn, name = ((lib.gnn_sage_gather_concat_live_bf16, "gnn_sage_gather_concat_live_bf16")
+                if _bf16(table) else
+                (lib.gnn_sage_gather_concat_live_f32, "gnn_sage_gather_concat_live_f32"))
+    _lib.check(fn(
         table.data_ptr(), table.stride(0), table.shape[0], self_idx.data_ptr(), idx.data_ptr(),
         idx.stride(0), M, _lib.ptr(live), k, F, mode, out.data_ptr(),
         out.stride(0), out[:, F:].data_ptr(), out.stride(0), err.data_ptr(),
-        _lib.stream_handle(table.device)), "gnn_sage_gather_concat_live_f32")
+        _lib.stream_handle(table.device)), name)
     if check:
         _check_err(err, "sage_gather_concat")
     return out
@@ -1728,18 +1765,30 @@ def sage_layer(table: torch.Tensor, nbr_idx: torch.Tensor, weight: torch.Tensor,
 
 def gather_rows(x: torch.Tensor, idx: torch.Tensor, out: torch.Tensor | None = None,
                 check: bool = True) -> torch.Tensor:
-    """out[i] = x[idx[i]] (torch.embedding semantics, one HIP launch)."""
+    """out[i] = x[idx[i]] (torch.embedding semantics, one HIP launch). The result has the
+    table's dtype, as torch.embedding's: a bfloat16 table gives bfloat16 rows
+    (gnn_gather_rows_bf16); a float32 ``out=`` view of a bfloat16 table selects the widening
+    gather (gnn_gather_rows_bf16_f32: ``x[idx].float()`` in the same launch)."""
+    _f32_or_bf16(x, "x")
     _require_device(x, idx, out)
-    x = _rows_f32(x, "x")
+    x = _rows_x(x, "x")
+    _bf16_inference_only(x, "gather_rows")
     idx = idx.to(torch.int64).contiguous().view(-1)
     n, F = idx.numel(), x.shape[1]
     if out is None:
-        out = torch.empty((n, F), dtype=torch.float32, device=x.device)
+        out = torch.empty((n, F), dtype=x.dtype, device=x.device)
+    elif _bf16(x) and out.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"out of a bfloat16 table must be bfloat16 or float32 (got {out.dtype})")
     err = _err_flag(x.device, check)
     lib = _lib.load()
-    _lib.check(lib.gnn_gather_rows_f32(x.data_ptr(), x.stride(0), x.shape[0], idx.data_ptr(), n, F,
-                                       out.data_ptr(), out.stride(0), err.data_ptr(),
-                                       _lib.stream_handle(x.device)), "gnn_gather_rows_f32")
+    if not _bf16(x):
+        fn, name = lib.gnn_gather_rows_f32, "gnn_gather_rows_f32"
+    elif _bf16(out):
+        fn, name = lib.gnn_gather_rows_bf16, "gnn_gather_rows_bf16"
+    else:
+        fn, name = lib.gnn_gather_rows_bf16_f32, "gnn_gather_rows_bf16_f32"
+    _lib.check(fn(x.data_ptr(), x.stride(0), x.shape[0], idx.data_ptr(), n, F, out.data_ptr(),
+                  out.stride(0), err.data_ptr(), _lib.stream_handle(x.device)), name)
     if check:
         _check_err(err, "gather_rows")
     return out

@@ -142,7 +142,12 @@ class collate_fn:
         self.device = torch.device(device if device is not None else "cuda:0")
         if self.device.type != "cuda":
             raise RuntimeError("collate_fn gathers on the ROCm device (no CPU fallback)")
-        self.feat_data = torch.as_tensor(feat_data, dtype=torch.float32).to(self.device).contiguous()
+        if isinstance(feat_data, torch.Tensor) and feat_data.dtype == torch.bfloat16:
+            # a bf16-stored table stays as it is: the gathered rows are bf16 (torch.embedding's
+            # dtype rule) and the aggregation widens them (gnn_sage_aggregate_bf16)
+            self.feat_data = feat_data.to(self.device).contiguous()
+        else:
+            self.feat_data = torch.as_tensor(feat_data, dtype=torch.float32).to(self.device).contiguous()
         self.num_layers = num_layers
         self.num_neighs = num_neighs
         self.is_gcn = is_gcn

@@ -873,6 +873,58 @@ int gnn_gather_rows_bf16(const uint16_t* x, int64_t ldx, int64_t n_x, const int6
                          void* stream);
 
 /*
+ * ---- GraphSAGE over a bf16-stored feature table (fp32 sums, fp32 / int64 results) ----
+ *
+ * The aggregation entries above (GraphSAGE/graph_utils.py:4-11, GraphSAGE.py:17, 47-49) with
+ * the node feature table -- or the pre-gathered neighbour tensor -- held as bf16: table / neigh
+ * are const uint16_t* (the bf16 bit patterns, what torch.bfloat16 stores), their pitches ldt /
+ * ld_k / ld_m count bf16 elements. Everything else is as in the _f32 twin of each entry: the
+ * argument list, the modes it takes, the validation (GNN_E_ARG), k == 0 -> GNN_E_UNSUPPORTED,
+ * M == 0 or feat == 0 -> GNN_OK, the error flag of an out-of-range index. Outputs stay fp32
+ * (MEAN, SUM, MAXPOOL, ARGMAX_F32, and the centre rows self_out of the concat forms, stored
+ * widened) or int64 (ARGMAX), with pitches in their own elements.
+ * A bf16 value is the high half of an fp32, so a loaded element widens exactly and in order:
+ * MEAN / SUM accumulate in fp32 exactly as the fp32 kernels do on the widened values, and
+ * MAXPOOL / ARGMAX are exact functions of the stored values (first maximum; a NaN counts as
+ * the maximum / propagates) -- bit-identical to the _f32 entry called on the widened table.
+ * Vector path (16-B loads, 8 bf16 per lane): feat % 8 == 0, ldt (ld_k, ld_m) % 8 == 0, the
+ * table 16-B aligned, and the outputs as on the fp32 vector path (ldo, ld_self % 4 == 0, fp32
+ * out / self_out 16-B aligned, an int64 out 32-B aligned); any other shape or view runs one
+ * element per lane. How a caller stores the table: round the fp32 features to bf16 once
+ * (round to nearest even; torch: table.to(torch.bfloat16)) and keep that copy -- half the
+ * memory of the fp32 table and half the bytes per gathered row. Hidden-layer tables (the fp32
+ * outputs of a layer) go through the _f32 entries.
+ */
+int gnn_sage_aggregate_bf16(const uint16_t* neigh, int64_t ld_k, int64_t ld_m, int64_t M,
+                            int64_t k, int64_t feat, int32_t mode, void* out, int64_t ldo,
+                            void* stream);
+int gnn_sage_gather_aggregate_bf16(const uint16_t* table, int64_t ldt, int64_t n_table,
+                                   const int64_t* idx, int64_t ldi, int64_t M, int64_t k,
+                                   int64_t feat, int32_t mode, void* out, int64_t ldo,
+                                   int32_t* err_flag, void* stream);
+int gnn_sage_gather_concat_bf16(const uint16_t* table, int64_t ldt, int64_t n_table,
+                                const int64_t* self_idx, const int64_t* idx, int64_t ldi,
+                                int64_t M, int64_t k, int64_t feat, int32_t mode, float* self_out,
+                                int64_t ld_self, float* out, int64_t ldo, int32_t* err_flag,
+                                void* stream);
+int gnn_sage_gather_concat_live_bf16(const uint16_t* table, int64_t ldt, int64_t n_table,
+                                     const int64_t* self_idx, const int64_t* idx, int64_t ldi,
+                                     int64_t M, const int64_t* live, int64_t k, int64_t feat,
+                                     int32_t mode, float* self_out, int64_t ld_self, float* out,
+                                     int64_t ldo, int32_t* err_flag, void* stream);
+
+/*
+ * Widening row gather: out[i, :feat] = (float) x[idx[i], :feat] over a bf16 table x (ldx in
+ * bf16 elements) into an fp32 out (ldo in floats) -- torch.embedding(x, idx).float() in one
+ * launch: the centre rows of a SageLayer whose neighbours come from another table. 16-B loads
+ * when feat, ldx % 8 == 0, ldo % 4 == 0 and x, out 16-B aligned, single elements otherwise.
+ * Arguments, validation and the error flag as gnn_gather_rows_f32.
+ */
+int gnn_gather_rows_bf16_f32(const uint16_t* x, int64_t ldx, int64_t n_x, const int64_t* idx,
+                             int64_t n, int64_t feat, float* out, int64_t ldo, int32_t* err_flag,
+                             void* stream);
+
+/*
  * Hashed element dropout fused with a row gather, replacing F.dropout(x, p, training) at
  * GAT/models/GAT.py:15,17 in training (and its backward): r = idx ? idx[i] : i,
  * out[i, c] = x[r, c] / (1 - p) when the (seed, key, c) hash clears p (common.hpp

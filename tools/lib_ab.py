@@ -3,6 +3,7 @@ build.build_variant) on the default SpMM path (ops.spmm_forward) at one workload
 
     python tools/lib_ab.py --build --variants base,ntcold      (CPU side)
     python tools/lib_ab.py --variants base,ntcold [--workload cfg2|ns] [--feat 128]
+    python tools/lib_ab.py --op sage --dtype bf16 --workload ns --variants base,sbu4,sbu16
 """
 import argparse
 import json
@@ -65,6 +66,10 @@ VARIANTS = {
     "su8": ["GNN_SAGE_U=8"],
     "su16": ["GNN_SAGE_U=16"],
     "su4": ["GNN_SAGE_U=4"],
+    # the same knob of the bf16-table instance (sage_bf16.hip; --op sage --dtype bf16)
+    "sbu4": ["GNN_SAGE_BF16_U=4"],
+    "sbu8": ["GNN_SAGE_BF16_U=8"],
+    "sbu16": ["GNN_SAGE_BF16_U=16"],
     # edge (col, val) moved to the edge slots by v_readlane + select instead of ds_bpermute:
     # slower (cfg2 0.946 vs 0.870 ms, ns 11.87 vs 11.79 ms, profiles/r05u_readlane_*.log)
     "readlane": ["GNN_SPMM_READLANE=1"],
@@ -78,7 +83,7 @@ def main():
     ap.add_argument("--workload", default="cfg2")
     ap.add_argument("--feat", type=int, default=128)
     ap.add_argument("--rounds", type=int, default=6)
-    ap.add_argument("--only", default="spmm.hip,sage.hip",
+    ap.add_argument("--only", default="spmm.hip,sage.hip,sage_bf16.hip",
                     help="--build: csrc files compiled with the variant's defines (the rest "
                          "link from the main build)")
     ap.add_argument("--seg-lens", default="", help="also time the default build at these seg_len")
@@ -87,6 +92,8 @@ def main():
     ap.add_argument("--op", default="spmm", choices=["spmm", "sage"],
                     help="sage: the fused gather-mean over [M=62,401, k=10] uniform-degree-weighted "
                          "samples of the workload's graph (the cfg4 layer-0 shape)")
+    ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16"],
+                    help="element type of the gathered table X")
     args = ap.parse_args()
     names = args.variants.split(",")  # "tag" or "tag@seg_len"
     if args.build:
@@ -109,6 +116,8 @@ def main():
         o = column_order(g, F)
         g = g if o is None else o.graph
     X = torch.randn(n, F, device=dev)
+    if args.dtype == "bf16":
+        X = X.bfloat16()
     Y = torch.empty(n, F, device=dev)
     nbytes = g.nnz * (8 + 4 * F) + n * (8 + 4 * F)
     if args.op == "sage":
@@ -119,7 +128,7 @@ def main():
         nodes = cand[torch.randperm(cand.numel(), device=dev)[:62401]]
         idx = sample_neighbors(g, nodes, 10, 0)
         Y = torch.empty(idx.shape[0], F, device=dev)
-        nbytes = idx.numel() * (4 * F + 8) + idx.shape[0] * 4 * F
+        nbytes = idx.numel() * (X.element_size() * F + 8) + idx.shape[0] * 4 * F
 
         def spmm_forward(g_, X_, out=None, seg_len=None):  # noqa: F811 -- same harness
             return sage_gather_aggregate(X_, idx, "MEAN", check=False, out=out)
@@ -147,7 +156,9 @@ def main():
             times[v].append(a.elapsed_time(b) / (20 if args.op == "sage" else 5))
     for v, t in times.items():
         m = statistics.median(t)
-        print(json.dumps({"variant": v, "op": args.op, "workload": args.workload, "feat": F, "median_ms": m,
+        print(json.dumps({"variant": v, "op": args.op, "dtype": args.dtype,
+                          "workload": args.workload, "feat": F, "median_ms": m,
+                          "min_ms": min(t), "max_ms": max(t),
                           "algo_GBps": nbytes / m / 1e6}), flush=True)
 
 
