@@ -267,6 +267,10 @@ SIGNATURES: dict[str, tuple] = {
     "gnn_gcn_adjacency_fill": (ctypes.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "gnn_sample_neighbors": (ctypes.c_int, [_vp, _vp, _i64, _vp, _i64, _i64, ctypes.c_uint64, _vp,
                                             _vp, _vp]),
+    "gnn_sample_contexts": (ctypes.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, ctypes.c_uint64,
+                                           _vp, _vp, _vp]),
+    "gnn_sample_negatives": (ctypes.c_int, [_vp, _i64, _vp, _i64, _i64, _i64, ctypes.c_uint64, _vp,
+                                            _vp, _vp]),
     "gnn_frontier_workspace_bytes": (ctypes.c_int64, [_i64]),
     "gnn_frontier_build": (ctypes.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp]),
     "gnn_frontier_emit": (ctypes.c_int, [_i64, _vp, _vp, _vp]),
@@ -291,6 +295,8 @@ SIGNATURES: dict[str, tuple] = {
     "gnn_py_layer_result_shape": (ctypes.c_int, [_vp, _vp]),
     "gnn_py_layer_result_copy": (ctypes.c_int, [_vp, _vp, _vp]),
     "gnn_py_layer_result_free": (None, [_vp]),
+    "gnn_py_context_nodes": (ctypes.c_int, [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp]),
+    "gnn_py_negative_nodes": (ctypes.c_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
     "gnn_pyset_order": (ctypes.c_int, [_vp, _i64, _vp, _vp]),
     "gnn_pyset_union_order": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _vp]),
 }

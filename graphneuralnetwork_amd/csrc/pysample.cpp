@@ -1,7 +1,8 @@
 // pysample.cpp -- bit-exact host restatement of the reference GraphSAGE sampler.
 //
 // Replaces get_layer_adj_nodes (GraphSAGE/data_utils.py:82-124), the index-map half of
-// collate_fn (:127-162), and the adj_lists construction of read_pubmed_data (:29-37).
+// collate_fn (:127-162), the adj_lists construction of read_pubmed_data (:29-37), and the
+// unsupervised dataset's get_context_nodes / get_negative_nodes (:50-70).
 //
 // The reference draws from CPython's global `random` (MT19937) and iterates Python
 // sets, so its index maps depend on
@@ -473,4 +474,88 @@ extern "C" int gnn_py_layer_result_copy(const void* result, int64_t* neigh_map,
 
 extern "C" void gnn_py_layer_result_free(void* result) {
   delete static_cast<LayerResult*>(result);
+}
+
+// get_context_nodes (data_utils.py:50-58): list(adj_lists[node])[:window] above `window`
+// neighbours, else random.choices(list(adj_lists[node]), k=window)
+extern "C" int gnn_py_context_nodes(const int64_t* rowptr, const int64_t* nbr, int64_t n_nodes,
+                                    const int64_t* nodes, int64_t n, int64_t window,
+                                    uint32_t* mt_state, int64_t* out) {
+  if (rowptr == nullptr || mt_state == nullptr || n_nodes < 0 || n < 0 || window < 0 ||
+      (n > 0 && nodes == nullptr) || (n > 0 && window > 0 && out == nullptr) ||
+      mt_state[624] > 624)
+    return GNN_E_ARG;
+  for (int64_t i = 0; i < n; ++i)
+    if (nodes[i] < 0 || nodes[i] >= n_nodes) return GNN_E_ARG;
+  try {
+    Mt rng;
+    memcpy(rng.mt, mt_state, sizeof(rng.mt));
+    rng.index = static_cast<int>(mt_state[624]);
+    std::vector<int64_t> draw;
+    int status = GNN_OK;
+    for (int64_t i = 0; i < n && status == GNN_OK; ++i) {
+      const int64_t* nb = nbr + rowptr[nodes[i]];
+      const int64_t deg = rowptr[nodes[i] + 1] - rowptr[nodes[i]];
+      if (deg > window) {
+        std::copy(nb, nb + window, out + i * window);
+      } else {
+        draw.clear();
+        if (!py_choices(rng, nb, deg, window, draw)) status = GNN_E_EMPTY;
+        else std::copy(draw.begin(), draw.end(), out + i * window);
+      }
+    }
+    memcpy(mt_state, rng.mt, sizeof(rng.mt));  // advanced as the reference's, also on IndexError
+    mt_state[624] = static_cast<uint32_t>(rng.index);
+    return status;
+  } catch (const std::bad_alloc&) {
+    return GNN_E_NOMEM;
+  }
+}
+
+// get_negative_nodes (data_utils.py:61-70) over all_nodes = range(n_all): per row
+// `while len(negatives) < len(contexts) * K: neg = random.choice(all_nodes); ...`
+extern "C" int gnn_py_negative_nodes(const int64_t* contexts, int64_t n, int64_t window,
+                                     int64_t n_all, int64_t K, uint32_t* mt_state, int64_t* out,
+                                     int64_t* bad_row) {
+  if (mt_state == nullptr || bad_row == nullptr || n < 0 || window < 0 || K < 0 || n_all <= 0 ||
+      n_all > 0xffffffffLL || mt_state[624] > 624)
+    return GNN_E_ARG;
+  const int64_t need = window * K;
+  if ((n > 0 && window > 0 && contexts == nullptr) || (n > 0 && need > 0 && out == nullptr))
+    return GNN_E_ARG;
+  *bad_row = -1;
+  try {
+    Mt rng;
+    memcpy(rng.mt, mt_state, sizeof(rng.mt));
+    rng.index = static_cast<int>(mt_state[624]);
+    std::vector<int64_t> distinct;
+    int status = GNN_OK;
+    for (int64_t i = 0; i < n; ++i) {
+      const int64_t* ctx = contexts + i * window;
+      // the reference never returns when fewer than `need` ids are allowed: refuse the row
+      distinct.clear();
+      for (int64_t j = 0; j < window; ++j)
+        if (ctx[j] >= 0 && ctx[j] < n_all &&
+            std::find(distinct.begin(), distinct.end(), ctx[j]) == distinct.end())
+          distinct.push_back(ctx[j]);
+      if (n_all - static_cast<int64_t>(distinct.size()) < need) {
+        *bad_row = i;
+        status = GNN_E_UNSUPPORTED;
+        break;
+      }
+      int64_t* neg = out + i * need;
+      int64_t cnt = 0;
+      while (cnt < need) {
+        const int64_t c = rng.randbelow(n_all);
+        if (std::find(ctx, ctx + window, c) == ctx + window &&
+            std::find(neg, neg + cnt, c) == neg + cnt)
+          neg[cnt++] = c;
+      }
+    }
+    memcpy(mt_state, rng.mt, sizeof(rng.mt));
+    mt_state[624] = static_cast<uint32_t>(rng.index);
+    return status;
+  } catch (const std::bad_alloc&) {
+    return GNN_E_NOMEM;
+  }
 }

@@ -15,6 +15,10 @@ tests/golden/pysampler.npz, made by running the reference).  ``collate_fn`` then
 gathers the feature rows on the device (``gnn_gather_rows_f32``) instead of
 ``torch.embedding`` on the host.  For throughput without CPython-stream parity, the
 device sampler is ``graphneuralnetwork_amd.sampler`` (structural parity only).
+
+``get_context_nodes`` / ``get_negative_nodes`` (data_utils.py:50-70, the unsupervised
+dataset's precomputation) are restated the same way and pinned by
+tests/golden/unsup_pairs.npz.
 """
 from __future__ import annotations
 
@@ -126,6 +130,85 @@ def get_layer_adj_nodes(nodes, adj_lists, num_layers, num_neighs, is_gcn, rng=No
     finally:
         lib.gnn_py_layer_result_free(res)
     return torch.from_numpy(neigh), torch.from_numpy(center)
+
+
+def _mt_state(rng):
+    """(generator, its getstate() pieces, the 625 MT words as a writable uint32 array)."""
+    r = _random if rng is None else rng
+    version, words, gauss = r.getstate()
+    mt = np.asarray(words, dtype=np.uint32)
+    if mt.size != _MT_WORDS:
+        raise ValueError("unexpected random state layout")
+    return r, version, gauss, mt
+
+
+def get_context_nodes(nodes, adj_lists, window_size, rng=None):
+    """GraphSAGE/data_utils.py:50-58, consuming ``rng`` (default: the global ``random``) as the
+    reference does -- one ``random()`` per ``random.choices`` draw -- and leaving it in the same
+    state. Returns the reference's list of lists: ``list(adj_lists[node])[:window_size]`` for a
+    node with more than ``window_size`` neighbours (the set's iteration order, from
+    ``PyAdjacency``), else ``window_size`` draws with replacement. A node without neighbours
+    raises the reference's IndexError."""
+    adj = _as_adjacency(adj_lists)
+    nodes = np.ascontiguousarray(np.asarray(list(nodes), dtype=np.int64))
+    window = int(window_size)
+    if window < 0:
+        raise ValueError("window_size must not be negative")
+    if nodes.size and (nodes.min() < 0 or nodes.max() >= adj.n_nodes):
+        raise IndexError("get_context_nodes: node id out of range")
+    r, version, gauss, mt = _mt_state(rng)
+    out = np.empty((nodes.size, window), dtype=np.int64)
+    rc = _lib.load().gnn_py_context_nodes(adj.rowptr.ctypes.data, adj.nbr.ctypes.data, adj.n_nodes,
+                                          nodes.ctypes.data, nodes.size, window, mt.ctypes.data,
+                                          out.ctypes.data)
+    r.setstate((version, tuple(int(w) for w in mt), gauss))  # advanced like the reference's
+    if rc == -4:
+        raise IndexError("Cannot choose from an empty sequence")
+    _lib.check(rc, "gnn_py_context_nodes")
+    return out.tolist()
+
+
+def get_negative_nodes(all_contexts, all_nodes, K, rng=None):
+    """GraphSAGE/data_utils.py:61-70 for ``all_nodes = range(n)`` (or a list equal to it: the
+    reference's only call site passes ``list(range(len(adj_lists)))``), consuming ``rng``
+    exactly: one ``random.choice`` (``_randbelow_with_getrandbits``) per candidate. Returns the
+    reference's list of lists, ``len(contexts) * K`` negatives per row.
+
+    The one deviation: a row on which the reference never returns -- fewer than
+    ``len(contexts) * K`` ids of ``all_nodes`` lie outside its contexts -- raises ValueError
+    before a draw is consumed for it (the generator stands where the rows before it left it)."""
+    n_all = len(all_nodes)
+    if not isinstance(all_nodes, range):
+        if not np.array_equal(np.asarray(all_nodes, dtype=np.int64), np.arange(n_all)):
+            raise ValueError("get_negative_nodes: all_nodes must be range(n) "
+                             "(an explicit id list is not supported)")
+    elif all_nodes != range(n_all):
+        raise ValueError("get_negative_nodes: all_nodes must be range(n)")
+    ctx = np.asarray(all_contexts, dtype=np.int64)
+    if ctx.size == 0:
+        ctx = ctx.reshape(len(all_contexts), 0)
+    if ctx.ndim != 2:
+        raise ValueError("get_negative_nodes: every row needs the same number of contexts")
+    ctx = np.ascontiguousarray(ctx)
+    K = int(K)
+    n, window = ctx.shape
+    if n == 0 or window * K <= 0:
+        return [[] for _ in range(n)]
+    if n_all == 0:  # random.choice([])
+        raise IndexError("Cannot choose from an empty sequence")
+    r, version, gauss, mt = _mt_state(rng)
+    out = np.empty((n, window * K), dtype=np.int64)
+    bad = ctypes.c_int64(-1)
+    rc = _lib.load().gnn_py_negative_nodes(ctx.ctypes.data, n, window, n_all, K, mt.ctypes.data,
+                                           out.ctypes.data, ctypes.byref(bad))
+    if rc == -3:
+        r.setstate((version, tuple(int(w) for w in mt), gauss))
+        raise ValueError(f"get_negative_nodes: row {bad.value} has fewer than {window * K} ids "
+                         f"of range({n_all}) outside its contexts (the reference would not "
+                         "return)")
+    _lib.check(rc, "gnn_py_negative_nodes")
+    r.setstate((version, tuple(int(w) for w in mt), gauss))
+    return out.tolist()
 
 
 class collate_fn:

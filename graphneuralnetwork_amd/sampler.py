@@ -15,6 +15,13 @@ aggregation gathers straight from the feature table (gnn_sage_gather_aggregate_f
 Per-hop fanouts ([25, 10], or any number of layers) are supported.  The reference's set iteration order
 and Mersenne-Twister draws are not reproduced (it is unseeded); the sampled
 distribution is (tests/test_sampler_gpu.py).
+
+The unsupervised branch (the reference's default) is here too: ``sample_contexts`` /
+``sample_negatives`` restate get_context_nodes / get_negative_nodes (data_utils.py:50-70) for a
+batch or for every training node at once (csrc/unsup.hip), and ``sample_unsupervised_batch``
+builds collate_fn's two towers -- the seeds, and ``contexts + negatives`` row by row -- as two
+``sample_batch`` calls whose ``forward_args`` are the 9 arguments of ``GraphSAGE.forward``
+(tests/test_unsup_sampler_gpu.py).
 """
 from __future__ import annotations
 
@@ -44,6 +51,21 @@ def stream_seed(seed: int, layer: int) -> int:
     """The device RNG key of one (batch seed, layer) pair: hashed, so batch s's layer 1
     and batch s+1's layer 0 draw independently (seed + layer would collide)."""
     return _mix64(_mix64(int(seed) & _M64) ^ ((int(layer) * 0xD1B54A32D192ED03) & _M64))
+
+
+def uniform_below(key: int, pos: int, draw: int, n: int) -> int:
+    """The device RNG's integer in [0, n) for (stream key, position, draw): a host restatement
+    of sample_kernels.hpp's ``uniform_below`` (``key`` = ``stream_seed(seed, layer)``)."""
+    r = _mix64(key ^ _mix64((int(pos) * 0x100000001B3 + int(draw)) & _M64))
+    if n <= 0xFFFFFFFF:
+        return ((r >> 32) * n) >> 32
+    return r % n
+
+
+# stream_seed layer tags of the unsupervised batch's draws: far above any hop index, so a
+# batch's contexts and negatives never share a stream with one of its hops
+CONTEXT_LAYER = 1 << 20
+NEGATIVE_LAYER = (1 << 20) + 1
 
 
 def _sample_into(adj: CsrGraph, nodes: torch.Tensor, k: int, seed: int, layer: int,
@@ -390,6 +412,178 @@ def sample_batch_stepwise(adj: CsrGraph, seeds: torch.Tensor, fanouts=(25, 10), 
     batch = SampledBatch(seeds, layers[-1], nb, cmaps[::-1], nmaps[::-1], tuple(layers))
     _raise_sample_error(int(err.item()))
     return batch
+
+
+def _raise_unsup_error(e: int) -> None:
+    """The contexts / negatives error word (gnn_sample_contexts, gnn_sample_negatives)."""
+    if e & 2:
+        raise IndexError("sample_contexts: node id out of range")
+    if e & 1:  # random.choices(list(set()), k) in the reference
+        raise IndexError("Cannot choose from an empty sequence")
+    if e & 32:
+        raise ValueError("sample_negatives: a row has fewer than window * K ids outside its "
+                         "contexts (the reference's get_negative_nodes would not return)")
+    if e & 64:
+        raise RuntimeError("sample_negatives: a row's candidate stream reached its bound "
+                           "(internal error)")
+
+
+def _check_limits(rc: int, what: str) -> None:
+    if rc == _lib.E_UNSUPPORTED:
+        raise ValueError(f"{what}: needs 1 <= window <= 64 and 1 <= window * K <= 1024")
+    _lib.check(rc, what)
+
+
+def _contexts_into(adj: CsrGraph, nodes: torch.Tensor, window: int, seed: int,
+                   err: torch.Tensor) -> torch.Tensor:
+    """gnn_sample_contexts without a host synchronisation (the error bits go to ``err``)."""
+    if not adj.rowptr.is_cuda:
+        raise RuntimeError("sampling runs on the ROCm device only (no CPU fallback)")
+    nodes = nodes.to(device=adj.device, dtype=torch.int64).contiguous().view(-1)
+    window = int(window)
+    out = torch.empty((nodes.numel(), max(window, 0)), dtype=torch.int64, device=adj.device)
+    _check_limits(_lib.load().gnn_sample_contexts(
+        adj.rowptr.data_ptr(), adj.col.data_ptr(), adj.n_rows, nodes.data_ptr(), nodes.numel(),
+        None, window, stream_seed(seed, CONTEXT_LAYER), out.data_ptr(), err.data_ptr(),
+        _lib.stream_handle(adj.device)), "gnn_sample_contexts")
+    return out
+
+
+def _negatives_into(contexts: torch.Tensor, n_nodes: int, K: int, seed: int,
+                    err: torch.Tensor) -> torch.Tensor:
+    """gnn_sample_negatives without a host synchronisation (the error bits go to ``err``)."""
+    if not contexts.is_cuda:
+        raise RuntimeError("sampling runs on the ROCm device only (no CPU fallback)")
+    if contexts.dim() != 2:
+        raise ValueError("contexts must be [n, window]")
+    contexts = contexts.to(torch.int64).contiguous()
+    n, window = contexts.shape
+    need = window * int(K)
+    out = torch.empty((n, max(need, 0)), dtype=torch.int64, device=contexts.device)
+    _check_limits(_lib.load().gnn_sample_negatives(
+        contexts.data_ptr(), n, None, window, need, int(n_nodes),
+        stream_seed(seed, NEGATIVE_LAYER), out.data_ptr(), err.data_ptr(),
+        _lib.stream_handle(contexts.device)), "gnn_sample_negatives")
+    return out
+
+
+def sample_contexts(adj: CsrGraph, nodes: torch.Tensor, window: int = 5,
+                    seed: int = 0) -> torch.Tensor:
+    """[len(nodes), window] int64 positive contexts (get_context_nodes,
+    GraphSAGE/data_utils.py:50-58) for a batch or for every training node at once: the first
+    ``window`` neighbours of a node with more than ``window`` of them -- in CSR order, where
+    the reference has its set's iteration order -- else ``window`` draws with replacement,
+    keyed by (stream_seed(seed, CONTEXT_LAYER), position, column). A node without neighbours
+    raises the reference's IndexError; ``window`` outside [1, 64] raises ValueError."""
+    err = torch.zeros(1, dtype=torch.int32, device=adj.device)
+    out = _contexts_into(adj, nodes, window, seed, err)
+    _raise_unsup_error(int(err.item()))
+    return out
+
+
+def sample_negatives(contexts: torch.Tensor, n_nodes: int, K: int = 5,
+                     seed: int = 0) -> torch.Tensor:
+    """[n, window * K] int64 negatives for ``contexts`` [n, window] (get_negative_nodes over
+    ``range(n_nodes)``, GraphSAGE/data_utils.py:61-70): per row the first ``window * K``
+    accepted candidates of a stream of uniform ids, a candidate being accepted when it is
+    neither a context of the row nor already accepted. Where the reference would loop forever
+    (fewer than ``window * K`` ids outside the row's contexts) this raises ValueError;
+    ``window`` outside [1, 64] or ``window * K`` outside [1, 1024] raise ValueError too."""
+    err = torch.zeros(1, dtype=torch.int32, device=contexts.device)
+    out = _negatives_into(contexts, n_nodes, K, seed, err)
+    _raise_unsup_error(int(err.item()))
+    return out
+
+
+@dataclass
+class UnsupervisedBatch:
+    """The device form of collate_fn's unsupervised output (GraphSAGE/data_utils.py:130-152):
+    the centre tower over ``seeds`` and the second tower over ``[contexts_b | negatives_b]``
+    row by row (B * S ids, S = window * (1 + K), duplicates kept), each a ``SampledBatch``."""
+    seeds: torch.Tensor        # [B]
+    contexts: torch.Tensor     # [B, window]
+    negatives: torch.Tensor    # [B, window * K]
+    center: SampledBatch       # the tower of the seeds
+    context: SampledBatch      # the tower of cat[contexts, negatives] (row-major)
+    labels: torch.Tensor       # [B, S] int64: window ones, then window * K zeros
+    # sync=False: the contexts / negatives error word (device int32) and the stream it was
+    # written on; None once read (or when both lists were given)
+    _err: torch.Tensor | None = None
+    _stream: object = None
+
+    @property
+    def pending(self) -> bool:
+        """True while the host has not read the error bits / the towers' sizes."""
+        return self._err is not None or self.center.pending or self.context.pending
+
+    def sync(self) -> "UnsupervisedBatch":
+        """This batch with both towers at their real sizes. Raises what the draws found: the
+        contexts' / negatives' error first, then the towers' (as sync=True does)."""
+        if not self.pending:
+            return self
+        if self._err is not None:
+            with torch.cuda.stream(self._stream):
+                e = int(self._err.item())
+            _raise_unsup_error(e)
+        return UnsupervisedBatch(self.seeds, self.contexts, self.negatives, self.center.sync(),
+                                 self.context.sync(), self.labels)
+
+    def check(self) -> None:
+        """Raise the samplers' error, if any (a pending batch's host reads)."""
+        self.sync()
+
+    def forward_args(self, table: torch.Tensor):
+        """The 9 arguments of GraphSAGE.forward (unsupervised branch); the last is
+        ``labels.shape``. A pending batch's arguments carry the device sizes."""
+        return (*self.center.forward_args(table), *self.context.forward_args(table),
+                tuple(self.labels.shape))
+
+
+def _rows_for(t, B: int, dev, what: str) -> torch.Tensor:
+    t = torch.as_tensor(t).to(device=dev, dtype=torch.int64)
+    if t.dim() != 2 or t.shape[0] != B:
+        raise ValueError(f"{what} must hold one row per seed ([{B}, width])")
+    return t.contiguous()
+
+
+def sample_unsupervised_batch(adj: CsrGraph, seeds: torch.Tensor, fanouts=(25, 10),
+                              window: int = 5, K: int = 5, seed: int = 0, gcn: bool = False,
+                              contexts=None, negatives=None,
+                              sync: bool = True) -> UnsupervisedBatch:
+    """One unsupervised GraphSAGE batch on the device: what the reference builds from
+    get_context_nodes / get_negative_nodes (its precomputed dataset) and collate_fn's
+    unsupervised branch (GraphSAGE/data_utils.py:50-70, :130-152).
+
+    ``contexts`` / ``negatives`` given ([B, window] / [B, window * K] rows for these seeds,
+    the precomputed dataset) are used as they are; ``None`` draws them for this batch
+    (``sample_contexts`` / ``sample_negatives`` with ``seed``). The second tower's seeds are
+    ``cat[contexts, negatives]`` row by row; both towers are ``sample_batch(..., seed)``.
+
+    ``sync=False``: nothing is read back -- both towers are pending, the contexts' /
+    negatives' error bits stay on the device, and the inference forward can be enqueued right
+    behind; ``check()`` / ``sync()`` read everything (flawed rows are -1 until then, and the
+    range-checked gathers read nothing outside the table)."""
+    if not adj.rowptr.is_cuda:
+        raise RuntimeError("sampling runs on the ROCm device only (no CPU fallback)")
+    dev = adj.device
+    seeds = seeds.to(device=dev, dtype=torch.int64).contiguous().view(-1)
+    B = seeds.numel()
+    err = None
+    if contexts is None or negatives is None:
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+    ctx = (_rows_for(contexts, B, dev, "contexts") if contexts is not None
+           else _contexts_into(adj, seeds, window, seed, err))
+    neg = (_rows_for(negatives, B, dev, "negatives") if negatives is not None
+           else _negatives_into(ctx, adj.n_rows, K, seed, err))
+    if err is not None and sync:
+        _raise_unsup_error(int(err.item()))
+        err = None
+    labels = torch.cat([torch.ones_like(ctx), torch.zeros_like(neg)], dim=1)
+    second = torch.cat([ctx, neg], dim=1).view(-1)
+    center = sample_batch(adj, seeds, fanouts, seed, gcn, sync)
+    context = sample_batch(adj, second, fanouts, seed, gcn, sync)
+    return UnsupervisedBatch(seeds, ctx, neg, center, context, labels, err,
+                             torch.cuda.current_stream(dev) if err is not None else None)
 
 
 def degree_ordered(adj: CsrGraph, table: torch.Tensor | None = None):

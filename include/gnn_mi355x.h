@@ -953,6 +953,43 @@ int gnn_sample_neighbors(const int64_t* rowptr, const int32_t* col, int64_t n_gr
                          int32_t* err_flag, void* stream);
 
 /*
+ * Positive contexts of an unsupervised GraphSAGE batch (get_context_nodes,
+ * GraphSAGE/data_utils.py:50-58): out[i, 0..window) for nodes[i], int64 [n, window]:
+ *     deg >  window: the first `window` entries of the node's CSR row (the reference takes the
+ *                    first `window` of list(set): a fixed subset, here in CSR order);
+ *     deg <= window: window draws with replacement (random.choices; deg == window too, the
+ *                    reference's test is a strict >): col[rowptr[v] + draw(seed, i, l, deg)];
+ *     deg == 0: row of -1 and *err_flag |= 1; node id outside [0, n_graph): row of -1,
+ *               *err_flag |= 2 (gnn_sample_neighbors' bits).
+ * The draws are gnn_sample_neighbors' counter RNG keyed by (seed, i, column). n_dev (nullable,
+ * DEVICE int64): only rows [0, min(*n_dev, n)) are written. 1 <= window <= 64, else
+ * GNN_E_UNSUPPORTED.
+ */
+int gnn_sample_contexts(const int64_t* rowptr, const int32_t* col, int64_t n_graph,
+                        const int64_t* nodes, int64_t n, const int64_t* n_dev, int64_t window,
+                        uint64_t seed, int64_t* out, int32_t* err_flag, void* stream);
+
+/*
+ * Negatives of an unsupervised GraphSAGE batch (get_negative_nodes over the universe
+ * range(n_nodes), GraphSAGE/data_utils.py:61-70 -- its only call site passes
+ * list(range(len(adj_lists)))). contexts: int64 [n, window]; out: int64 [n, need]
+ * (need = window * K in the reference). Row i = the first `need` ACCEPTED candidates of the
+ * stream c_t = draw(seed, i, t, n_nodes), t = 0, 1, ..., where c_t is accepted iff it equals
+ * no context of row i and no earlier accepted candidate of row i (the centre node is not
+ * excluded, as in the reference): the reference's loop with the generator replaced, evaluated
+ * lane-parallel with the same result bit for bit.
+ * It never spins: a row whose d distinct contexts inside [0, n_nodes) leave
+ * n_nodes - d < need allowed ids (the reference loops forever) is a row of -1 and
+ * *err_flag |= 32; a feasible row's stream is cut after 64 * need + 4096 candidates
+ * (probability < 2^-64, csrc/unsup.hip), then *err_flag |= 64 and the row's tail is -1.
+ * Context ids outside [0, n_nodes) (a failed context row's -1) exclude nothing.
+ * n_dev as above. 1 <= window <= 64 and 1 <= need <= 1024, else GNN_E_UNSUPPORTED.
+ */
+int gnn_sample_negatives(const int64_t* contexts, int64_t n, const int64_t* n_dev, int64_t window,
+                         int64_t need, int64_t n_nodes, uint64_t seed, int64_t* out,
+                         int32_t* err_flag, void* stream);
+
+/*
  * Batch frontier (sampler.sample_batch): the sorted distinct ids of two id lists and the
  * position of listed ids among them -- collate_fn's set union and index remap
  * (GraphSAGE/data_utils.py:100-116), i.e. torch.unique(cat[a, b]) + torch.searchsorted.
@@ -1046,6 +1083,19 @@ int gnn_gcn_adjacency_fill(const void* workspace, int64_t n_edges, int64_t n_nod
  *                        GNN_E_EMPTY: a sampled node has no neighbours (IndexError).
  *   gnn_pyset_order / gnn_pyset_union_order: iteration order of set(keys) and of
  *                        set(a).union(set(b)) (test hooks for the set restatement).
+ *   gnn_py_context_nodes get_context_nodes(nodes, adj_lists, window) (data_utils.py:50-58):
+ *                        out int64 [n, window]; list(adj_lists[v])[:window] above `window`
+ *                        neighbours, else random.choices (one random() per draw).
+ *                        GNN_E_EMPTY: a node without neighbours (the generator advanced by
+ *                        the one random() the reference consumes before it raises).
+ *   gnn_py_negative_nodes get_negative_nodes(all_contexts, range(n_all), K)
+ *                        (data_utils.py:61-70): contexts int64 [n, window], out int64
+ *                        [n, window * K]; one random.choice (_randbelow_with_getrandbits)
+ *                        per candidate. The one deviation: a row the reference would spin on
+ *                        (fewer than window * K ids of range(n_all) outside its contexts)
+ *                        returns GNN_E_UNSUPPORTED with *bad_row = its index, before a draw
+ *                        is consumed for it (the rows before it are written, the generator
+ *                        stands where they left it). 0 < n_all < 2^32.
  * Keys are node ids in [0, 2^61 - 1). */
 int gnn_pyadj_build(const int64_t* src, const int64_t* dst, int64_t n_pairs, int64_t n_nodes,
                     int64_t* rowptr, int64_t* nbr);
@@ -1055,6 +1105,11 @@ int gnn_py_layer_sample(const int64_t* rowptr, const int64_t* nbr, int64_t n_nod
 int gnn_py_layer_result_shape(const void* result, int64_t* dims);
 int gnn_py_layer_result_copy(const void* result, int64_t* neigh_map, int64_t* center_map);
 void gnn_py_layer_result_free(void* result);
+int gnn_py_context_nodes(const int64_t* rowptr, const int64_t* nbr, int64_t n_nodes,
+                         const int64_t* nodes, int64_t n, int64_t window, uint32_t* mt_state,
+                         int64_t* out);
+int gnn_py_negative_nodes(const int64_t* contexts, int64_t n, int64_t window, int64_t n_all,
+                          int64_t K, uint32_t* mt_state, int64_t* out, int64_t* bad_row);
 int gnn_pyset_order(const int64_t* keys, int64_t n, int64_t* out, int64_t* n_out);
 int gnn_pyset_union_order(const int64_t* a, int64_t na, const int64_t* b, int64_t nb,
                           int64_t* out, int64_t* n_out);
