@@ -105,6 +105,14 @@ SIGNATURES: dict[str, tuple] = {
                                                          _i64, _vp, _vp]),
     "gnn_gather_rows_bf16_f32": (ctypes.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _vp,
                                                 _vp]),
+    # the training SageLayer's backward (sage_bwd.hip)
+    "gnn_sage_maps_transpose_workspace_bytes": (_i64, [_i64, _i64]),
+    "gnn_sage_maps_transpose": (ctypes.c_int, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp,
+                                               _vp, _i64, _vp]),
+    "gnn_sage_scatter_concat_supported": (ctypes.c_int, [_i64]),
+    "gnn_sage_scatter_concat_workspace_bytes": (_i64, [_i64, _i64, _i64]),
+    "gnn_sage_scatter_concat_f32": (ctypes.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64,
+                                                   _vp, _i64, _vp, _i64, _vp]),
     "gnn_halo_alltoallv_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
     "gnn_halo_rccl_path": (ctypes.c_int, [ctypes.c_char_p, _i64]),
     "gnn_spmm_plan_scratch_bytes": (_i64, [_i64]),

@@ -13,7 +13,11 @@ Hot path on gfx950:
   never materialises the [M, k, H] neighbour tensor, plus one row-gather
   launch for the centre rows;
 * ``SageLayer``'s ``Linear(cat[self, agg])`` -> two accumulating MFMA GEMMs on
-  the two halves of W (no concatenated copy).
+  the two halves of W (no concatenated copy);
+* training on the device sampler's batches (``l.backward()``, train_eval.py:112-119) -> one
+  autograd function per MEAN layer (``_SageTrainLayerFn``): the inference launches forward,
+  the weight gradient in one masked pass and the concat gather's adjoint on the device
+  (``csrc/sage_bwd.hip``) backward.
 """
 from __future__ import annotations
 
@@ -24,9 +28,10 @@ import torch.nn.functional as F
 from torch import nn
 
 from .graph import from_coo
-from .ops import (_bf16_inference_only, gather_rows, gcn_transform, linear_relu_classify,
-                  sage_aggregate, sage_gather_aggregate, sage_gather_concat, sage_layer,
-                  spmm_forward)
+from .ops import (_bf16_inference_only, _masked_grad, _transform_or_mm, gather_rows,
+                  gcn_transform, gemm_tn_masked, linear_relu_classify, sage_aggregate,
+                  sage_gather_aggregate, sage_gather_concat, sage_layer, sage_maps_transpose,
+                  sage_scatter_concat, sage_train_layer_supported, spmm_forward)
 
 # the inference SageLayer GEMM relu([self | agg] @ W^T) runs on the hand-written MFMA kernel
 # (gnn_linear_relu_f32). With the split-bf16 arithmetic (the default, ops.set_transform_precision)
@@ -338,6 +343,73 @@ def _fused_sage_layer(block, center, neigh: Gathered, dense: nn.Linear | None = 
     return torch._addmm_activation(zero, buf, W.t())
 
 
+# The training SageLayer over a sampler batch as ONE autograd function (``_SageTrainLayerFn``).
+# False: the separate row gather, gather-mean and torch linear + addmm + relu, each with its own
+# backward (tools/sage_train_ab.py flips it to time both paths in one process).
+SAGE_TRAIN_FUSED = True
+
+
+class _SageTrainLayerFn(torch.autograd.Function):
+    """relu(W . cat[table[cidx], mean_j table[idx[:, j]]]) (GraphSAGE/GraphSAGE.py:17-20 over
+    the gathers of :47-49) with autograd w.r.t. W and, where it asks for it, the fp32 table.
+
+    Forward: the inference launches -- ``sage_gather_concat`` writes buf = [self | agg] (the
+    table fp32 or bf16), ``gcn_transform`` gives y = relu(buf W^T). Backward, with
+    dY' = dY . [y > 0]: dW = dY'^T buf in one masked pass (``gemm_tn_masked``); only for a table
+    that requires grad (the layers after the first) dBuf = dY' W and dX = the adjoint of the
+    concat gather, ``sage_scatter_concat`` over the device-built transposed maps
+    (``sage_maps_transpose``): no sort, CSR or value array built in Python, no float atomics.
+    The maps are the device sampler's (in range): nothing is checked, nothing read back."""
+
+    @staticmethod
+    def forward(ctx, table, W, cidx, idx):
+        buf = sage_gather_concat(table, cidx, idx, "MEAN", check=False)
+        y = gcn_transform(buf, W, relu=True)
+        if y is None:  # sage_train_layer_supported said the transform takes the shape
+            raise RuntimeError("the SageLayer transform refused a shape it reports as covered")
+        ctx.save_for_backward(buf, y, W, cidx, idx)
+        ctx.n_prev = table.shape[0]
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        buf, y, W, cidx, idx = ctx.saved_tensors
+        d_table = dW = g = None
+        if ctx.needs_input_grad[1]:
+            r = gemm_tn_masked(buf, dy, y, 1.0, False, trans=True)
+            if r is not None:
+                dW = r[0]
+            else:
+                g = _masked_grad(dy, y, 1.0)
+                dW = torch.mm(g.t(), buf)
+        if ctx.needs_input_grad[0]:
+            if g is None:
+                g = _masked_grad(dy, y, 1.0)
+            dbuf = _transform_or_mm(g, W.t().contiguous())
+            tr = sage_maps_transpose(cidx, idx, ctx.n_prev, check=False)
+            if tr is not None:
+                d_table = sage_scatter_concat(dbuf, tr, ctx.n_prev)
+            if d_table is None:  # a shape the kernel declines: the SpMM over a Python-built CSR
+                n = W.shape[1] // 2
+                d_table = (_scatter_rows(dbuf[:, :n], cidx.reshape(-1, 1), ctx.n_prev, 1.0)
+                           + _scatter_rows(dbuf[:, n:], idx, ctx.n_prev, 1.0 / idx.shape[1]))
+        return d_table, dW, None, None
+
+
+def _sage_train_layer(block, center: Gathered, neigh: Gathered):
+    """The training SageLayer on trusted maps over one table, or None where
+    ``_SageTrainLayerFn`` does not cover the layer (the caller takes the unfused path)."""
+    table, W = neigh.table, block.weight.weight
+    idx, cidx = neigh.index, center.index
+    if (idx.dim() != 2 or idx.dtype != torch.int64 or cidx.dtype != torch.int64
+            or cidx.numel() != idx.shape[0] or idx.shape[0] == 0
+            or not (W.requires_grad or table.requires_grad)
+            or (table.dtype == torch.bfloat16 and table.requires_grad)  # raises as before
+            or not sage_train_layer_supported(table, W, idx.shape[1])):
+        return None
+    return _SageTrainLayerFn.apply(table, W, cidx, idx)
+
+
 class GraphSAGE(nn.Module):
     """GraphSAGE/GraphSAGE.py:23-61 with the same 9-argument forward."""
 
@@ -366,6 +438,14 @@ class GraphSAGE(nn.Module):
                 and center.table is neigh.table
                 and neigh.table.dtype in (torch.float32, torch.bfloat16))
 
+    def _train_fused_ok(self, block, center, neigh) -> bool:
+        """The training layer (``_SageTrainLayerFn``): MEAN over cat[self, agg], centre and
+        neighbours Gathered over ONE table through the device sampler's (trusted) maps."""
+        return (SAGE_TRAIN_FUSED and torch.is_grad_enabled() and not block.gcn
+                and self.agg_func == 'MEAN' and isinstance(center, Gathered)
+                and isinstance(neigh, Gathered) and center.table is neigh.table
+                and center.trusted and neigh.trusted)
+
     def forward(self, center_feats_data, center_nodes_map, center_neigh_feats_data, center_neigh_nodes_map,
                 contexts_negatives_feats_data, contexts_negatives_nodes_map, contexts_negatives_neigh_feats_data,
                 contexts_negatives_neigh_nodes_map, contexts_negatives_shape):
@@ -382,9 +462,13 @@ class GraphSAGE(nn.Module):
                         feats_data, classes = feats_data
                 else:
                     center, neigh = _trim(center), _trim(neigh)
-                    if isinstance(center, Gathered):
-                        center = _gather(center.table, center.index, center.trusted)
-                    feats_data = block(center, Aggregator(neigh, self.agg_func))
+                    feats_data = None
+                    if self._train_fused_ok(block, center, neigh):
+                        feats_data = _sage_train_layer(block, center, neigh)
+                    if feats_data is None:
+                        if isinstance(center, Gathered):
+                            center = _gather(center.table, center.index, center.trusted)
+                        feats_data = block(center, Aggregator(neigh, self.agg_func))
                 if i != self.num_layers - 1:
                     cm = center_nodes_map[i]
                     nm = center_neigh_nodes_map[i]

@@ -6,6 +6,7 @@ library must be loadable, otherwise a RuntimeError is raised.
 from __future__ import annotations
 
 import contextlib
+from typing import NamedTuple
 
 import torch
 
@@ -1705,6 +1706,124 @@ def sage_gather_concat(table: torch.Tensor, self_idx: torch.Tensor, idx: torch.T
     if check:
         _check_err(err, "sage_gather_concat")
     return out
+
+
+class SageMapsT(NamedTuple):
+    """The transposed index maps of one SageLayer (``sage_maps_transpose``): the slots of
+    target t are ``slot[ptr[t]:ptr[t + 1]]`` in ascending slot order; slot s < M is centre row
+    s, slot s >= M the neighbour entry s - M (row (s - M) // k, column (s - M) % k)."""
+    ptr: torch.Tensor    # int64 [n_prev + 1]
+    slot: torch.Tensor   # int32 [M * (k + 1)]
+    M: int
+    k: int
+
+
+def sage_maps_transpose(center_idx: torch.Tensor, neigh_idx: torch.Tensor, n_prev: int,
+                        check: bool = True) -> SageMapsT | None:
+    """The transposed maps of ``sage_gather_concat(table, center_idx, neigh_idx)`` over a table
+    of ``n_prev`` rows, built on the device (gnn_sage_maps_transpose: a stable radix sort of
+    the slots by target): exactly numpy's stable argsort of ``[center_idx, neigh_idx.ravel()]``
+    with its bincount / cumsum. ``check``: an index outside [0, n_prev) raises IndexError (one
+    host read). None where M (k + 1) does not fit an int32 slot id."""
+    _require_device(center_idx, neigh_idx)
+    if neigh_idx.dim() != 2:
+        raise ValueError("neigh_idx must be [M, k]")
+    if center_idx.dtype != torch.int64 or neigh_idx.dtype != torch.int64:
+        raise TypeError("center_idx and neigh_idx must be int64")
+    n_prev = int(n_prev)
+    if n_prev < 0:
+        raise ValueError("n_prev must not be negative")
+    if ((neigh_idx.stride(1) != 1 and neigh_idx.shape[1] > 1)
+            or (neigh_idx.shape[0] > 1 and neigh_idx.stride(0) < neigh_idx.shape[1])):
+        neigh_idx = neigh_idx.contiguous()
+    center_idx = center_idx.contiguous().view(-1)
+    M, k = neigh_idx.shape
+    if center_idx.numel() != M:
+        raise ValueError("center_idx must hold one index per row of neigh_idx")
+    dev = neigh_idx.device
+    if M == 0:  # no slot: every list is empty
+        return SageMapsT(torch.zeros(n_prev + 1, dtype=torch.int64, device=dev),
+                         torch.empty(0, dtype=torch.int32, device=dev), 0, k)
+    lib = _lib.load()
+    nbytes = int(lib.gnn_sage_maps_transpose_workspace_bytes(M, k))
+    if nbytes == _lib.E_UNSUPPORTED or n_prev >= 2 ** 31 - 1:
+        return None
+    ptr = torch.empty(n_prev + 1, dtype=torch.int64, device=dev)
+    slot = torch.empty(M * (k + 1), dtype=torch.int32, device=dev)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    err = _err_flag(dev, check)
+    ldi = neigh_idx.stride(0) if M > 1 and k > 0 else k  # a single row's stride is never used
+    _lib.check(lib.gnn_sage_maps_transpose(
+        center_idx.data_ptr(), neigh_idx.data_ptr() if k > 0 else None, ldi, M, k, n_prev,
+        ptr.data_ptr(), slot.data_ptr(), err.data_ptr(), ws.data_ptr(), ws.numel(),
+        _lib.stream_handle(dev)), "gnn_sage_maps_transpose")
+    if check:
+        _check_err(err, "sage_maps_transpose")
+    return SageMapsT(ptr, slot, M, k)
+
+
+def sage_scatter_concat(dbuf: torch.Tensor, tr: SageMapsT, n_prev: int,
+                        out: torch.Tensor | None = None) -> torch.Tensor | None:
+    """The adjoint of ``sage_gather_concat`` in MEAN mode (gnn_sage_scatter_concat_f32):
+    dX[t] = sum of dbuf[s, :F] over the centre slots s of t + sum of dbuf[m, F:] / k over the
+    neighbour slots (m, j) of t, for the maps ``tr = sage_maps_transpose(...)``; float32
+    [n_prev, F] with F = dbuf.shape[1] // 2. Rows nobody references are zeros. fp32 sums in
+    slot order, no float atomics: bit-identical from run to run. ``dbuf``: any float32 [M, 2F]
+    view with 16-B aligned rows; ``out``: a contiguous float32 [n_prev, F] tensor to write
+    (every row is stored, whatever it held). None where the kernel does not take the shape
+    (F not a power of two in [4, 256], k = 0, a misaligned view): the caller scatters another
+    way."""
+    _require_device(dbuf, tr.ptr, tr.slot, out)
+    if dbuf.dtype != torch.float32:
+        raise TypeError(f"dbuf must be float32 (got {dbuf.dtype})")
+    if dbuf.dim() != 2 or dbuf.shape[1] % 2:
+        raise ValueError("dbuf must be [M, 2F]")
+    n_prev = int(n_prev)
+    M, k = tr.M, tr.k
+    F = dbuf.shape[1] // 2
+    if dbuf.shape[0] != M or tr.ptr.numel() != n_prev + 1 or tr.slot.numel() != M * (k + 1):
+        raise ValueError("dbuf, the transposed maps and n_prev do not belong together")
+    if tr.ptr.dtype != torch.int64 or tr.slot.dtype != torch.int32:
+        raise TypeError("the transposed maps must be (int64 ptr, int32 slot)")
+    if out is not None and (out.shape != (n_prev, F) or out.dtype != torch.float32
+                            or not out.is_contiguous() or out.data_ptr() % 16):
+        raise ValueError(f"out must be a contiguous float32 [{n_prev}, {F}] tensor")
+    lib = _lib.load()
+    if k == 0 or not lib.gnn_sage_scatter_concat_supported(F):
+        return None
+    if M == 0:
+        return (torch.zeros((n_prev, F), dtype=torch.float32, device=dbuf.device)
+                if out is None else out.zero_())
+    if (dbuf.stride(1) != 1 or (M > 1 and (dbuf.stride(0) % 4 or dbuf.stride(0) < 2 * F))
+            or dbuf.data_ptr() % 16):
+        return None
+    nbytes = int(lib.gnn_sage_scatter_concat_workspace_bytes(M, k, F))
+    if nbytes < 0:
+        return None
+    dx = out if out is not None else torch.empty((n_prev, F), dtype=torch.float32,
+                                                 device=dbuf.device)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dbuf.device)
+    ptr, slot = tr.ptr.contiguous(), tr.slot.contiguous()
+    _lib.check(lib.gnn_sage_scatter_concat_f32(
+        dbuf.data_ptr(), dbuf.stride(0) if M > 1 else 2 * F, ptr.data_ptr(), slot.data_ptr(), M, k,
+        F, n_prev, dx.data_ptr(), F, ws.data_ptr(), ws.numel(),
+        _lib.stream_handle(dbuf.device)), "gnn_sage_scatter_concat_f32")
+    return dx
+
+
+def sage_train_layer_supported(table: torch.Tensor, weight: torch.Tensor, k: int) -> bool:
+    """Whether the training SageLayer (graphsage._SageTrainLayerFn) runs on its own kernels for
+    an [n, F] table, an [H, 2F] weight and k neighbours per row: ``gcn_transform`` takes
+    (2F, H) and ``sage_scatter_concat`` takes F."""
+    if (not table.is_cuda or not weight.is_cuda or table.dim() != 2 or weight.dim() != 2
+            or table.dtype not in (torch.float32, torch.bfloat16)
+            or weight.dtype != torch.float32 or k < 1):
+        return False
+    F, (H, K) = table.shape[1], weight.shape
+    lib = _lib.load()
+    return bool(K == 2 * F and lib.gnn_gcn_transform_supported(K, H)
+                and (TRANSFORM_WIDE_MFMA or not (H == 256 and K > 64))
+                and lib.gnn_sage_scatter_concat_supported(F))
 
 
 # The fused layer is opt-in (set SAGE_FUSED_MIN_ROWS to the smallest frontier to fuse): at

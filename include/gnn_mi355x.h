@@ -925,6 +925,46 @@ int gnn_gather_rows_bf16_f32(const uint16_t* x, int64_t ldx, int64_t n_x, const 
                              void* stream);
 
 /*
+ * The backward of gnn_sage_gather_concat_f32 in MEAN mode (the training SageLayer,
+ * GraphSAGE/GraphSAGE.py:17, 47-49 under l.backward(), train_eval.py:112-119). The M (k + 1)
+ * contributions of a layer are numbered as slots: slot s < M is the centre row s (target
+ * cidx[s]), slot s >= M the neighbour entry e = s - M (row e / k, column e % k, target
+ * idx[e / k, e % k]).
+ *
+ * gnn_sage_maps_transpose: ptr (int64 [n_prev + 1]) and slot (int32 [M (k + 1)]): the slots of
+ *   target t are slot[ptr[t] : ptr[t + 1]] in ASCENDING slot order -- numpy's stable argsort of
+ *   the concatenated targets [cidx, idx.ravel()] with its bincount / cumsum, bit for bit. An
+ *   index outside [0, n_prev) sets bit 0 of *err_flag; its slot is placed past ptr[n_prev],
+ *   where the scatter never reads it. idx: row stride ldi >= k. M (k + 1) >= 2^31 or
+ *   n_prev >= 2^31 - 1: GNN_E_UNSUPPORTED (the workspace query returns it too).
+ *   workspace: gnn_sage_maps_transpose_workspace_bytes(M, k) bytes of device memory.
+ * gnn_sage_scatter_concat_f32: for every t < n_prev
+ *     dx[t, :F] = sum_{centre slots s of t} dbuf[s, 0:F]
+ *               + sum_{neighbour slots s of t} dbuf[(s - M) / k, F:2F] * (1 / k)
+ *   (dbuf fp32 [M, ldd >= 2 F], dx fp32 [n_prev, ldx >= F]). A target without a slot is written
+ *   as zeros: every row of dx is stored, nothing needs clearing first. fp32 sums in slot order;
+ *   a list of more than 256 slots is cut into chunks of 256 summed by separate wavefronts and
+ *   added in chunk order. No floating-point atomics: the result is a function of the
+ *   arguments alone, bit-identical from run to run. NaN / Inf propagate as in a plain sum.
+ *   gnn_sage_scatter_concat_supported(F): F a power of two in [4, 256] (F / 4 lanes of 16 B per
+ *   row); else GNN_E_UNSUPPORTED. dbuf, dx and the workspace 16-B aligned, ldd and ldx
+ *   multiples of 4 (GNN_E_ALIGN). ptr / slot as the builder writes them; entries that point
+ *   outside the arrays are skipped, never followed.
+ *   workspace: gnn_sage_scatter_concat_workspace_bytes(M, k, F) bytes of device memory.
+ */
+int64_t gnn_sage_maps_transpose_workspace_bytes(int64_t M, int64_t k);
+int gnn_sage_maps_transpose(const int64_t* cidx, const int64_t* idx, int64_t ldi, int64_t M,
+                            int64_t k, int64_t n_prev, int64_t* ptr, int32_t* slot,
+                            int32_t* err_flag, void* workspace, int64_t workspace_bytes,
+                            void* stream);
+int gnn_sage_scatter_concat_supported(int64_t feat);
+int64_t gnn_sage_scatter_concat_workspace_bytes(int64_t M, int64_t k, int64_t feat);
+int gnn_sage_scatter_concat_f32(const float* dbuf, int64_t ldd, const int64_t* ptr,
+                                const int32_t* slot, int64_t M, int64_t k, int64_t feat,
+                                int64_t n_prev, float* dx, int64_t ldx, void* workspace,
+                                int64_t workspace_bytes, void* stream);
+
+/*
  * Hashed element dropout fused with a row gather, replacing F.dropout(x, p, training) at
  * GAT/models/GAT.py:15,17 in training (and its backward): r = idx ? idx[i] : i,
  * out[i, c] = x[r, c] / (1 - p) when the (seed, key, c) hash clears p (common.hpp

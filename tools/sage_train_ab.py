@@ -1,0 +1,185 @@
+"""The GraphSAGE training step on the cfg4 dataset with and without the training layer
+(graphsage._SageTrainLayerFn), measured in one process.
+
+    python tools/sage_train_ab.py [--small] --out profiles/sage_train_ab_cfg4.json
+
+Builds the cfg4 workload as bench.py does (R-MAT 10M nodes / 100M edges, symmetric adjacency
+relabelled by degree, a 10M x 128 table; --small: 1M / 10M for a quick look), samples one batch
+of 8192 seeds with fanouts [25, 10] and times, with device events around blocks of calls, every
+side at least --seconds of timed work, median and min-max of the block means:
+
+  * the training step -- forward, loss, backward; the weights require grad, the table does not
+    -- (a) supervised with cross-entropy, (b) unsupervised with window 5, K 5 and
+    binary_cross_entropy_with_logits, each with graphsage.SAGE_TRAIN_FUSED off (the separate
+    gathers, torch's linear + addmm + relu and a CSR rebuilt in Python per backward gather) and
+    on, over an fp32 and a bf16 table, the four sides alternated;
+  * the two new launches alone at the second tower's layer-1 shape (its 245,760 seeds, k = 25,
+    over the ~1M-row frontier): ``sage_maps_transpose`` and ``sage_scatter_concat``, the
+    scatter's gathered bytes M (k + 1) F 4 over its time as a share of the 8 TB/s roofline,
+    and beside them what they replace: the two ``_scatter_rows`` calls and the sum of their
+    results (autograd's accumulation of the two gradients of one table).
+
+Each comparison also records that both sides compute the same numbers at this size: the largest
+difference of every weight gradient (one step per side) and of the scatter's output, over the
+largest magnitude of the previous path's.
+"""
+import argparse
+import json
+import statistics
+import sys
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+sys.path.insert(0, str(ROOT / "tools"))
+
+HBM_BYTES_PER_S = 8.0e12  # MI355X HBM3E peak, the roofline bench.py uses
+WINDOW, K = 5, 5
+
+
+def summary(ms):
+    return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms),
+            "blocks": len(ms)}
+
+
+def compare(t):
+    """{side: summary} plus, per table dtype, off / on and whether the block ranges are apart."""
+    out = {k: summary(v) for k, v in t.items()}
+    for dt in ("fp32", "bf16"):
+        off, on = out[f"{dt}_off"], out[f"{dt}_on"]
+        out[f"{dt}_off_over_on"] = off["median_ms"] / on["median_ms"]
+        out[f"{dt}_on_faster_outside_block_ranges"] = on["max_ms"] < off["min_ms"]
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--small", action="store_true", help="1M nodes / 10M edges (not cfg4)")
+    ap.add_argument("--feat", type=int, default=128)
+    ap.add_argument("--seeds", type=int, default=8192)
+    ap.add_argument("--seconds", type=float, default=1.0, help="timed work per side, at least")
+    ap.add_argument("--out", required=True)
+    args = ap.parse_args()
+    n, e = (1_000_000, 10_000_000) if args.small else (10_000_000, 100_000_000)
+    res = {}
+
+    def write():
+        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.out).write_text(json.dumps(res, indent=1) + "\n")
+
+    import torch
+    import torch.nn.functional as Fn
+    from graphneuralnetwork_amd import _lib, graphsage, ops
+    from graphneuralnetwork_amd import sampler as S
+    from graphneuralnetwork_amd.graphsage import GraphSAGE
+    from graphneuralnetwork_amd.rmat import rmat_edges
+    from spmm_bf16_ab import alternate
+    dev = torch.device("cuda:0")
+    F = H = args.feat
+    fanouts = (25, 10)
+    s, d = rmat_edges(n, e, 0)
+    adj = S.symmetric_adjacency(s, d, n, device=dev)
+    del s, d
+    adj, _, _ = S.degree_ordered(adj)
+    deg = adj.rowptr[1:] - adj.rowptr[:-1]
+    n_conn = int((deg > 0).sum())
+    gen = torch.Generator(device=dev).manual_seed(0)
+    table = torch.randn(n, F, device=dev, generator=gen)
+    table16 = table.bfloat16()
+    print("dataset built", flush=True)
+    B = args.seeds
+    seeds = torch.randperm(n_conn, device=dev, generator=gen)[:B]
+    ctx_b = S.sample_contexts(adj, seeds, WINDOW, seed=0)
+    neg_b = S.sample_negatives(ctx_b, n_conn, K, seed=0)  # among the nodes with neighbours
+    pu = S.sample_unsupervised_batch(adj, seeds, fanouts, WINDOW, K, seed=1, contexts=ctx_b,
+                                     negatives=neg_b)
+    ps = S.sample_batch(adj, seeds, fanouts, seed=1)
+    res.update({"workload": "cfg4" if not args.small else "small", "nodes": n, "edges": e,
+                "feat": F, "hidden": H, "seeds": B, "window": WINDOW, "K": K,
+                "fanout": list(fanouts), "device": torch.cuda.get_device_name(dev),
+                "library_stamp": _lib.load().gnn_build_stamp().decode(),
+                "centre_tower_layers": list(pu.center.layer_sizes),
+                "second_tower_layers": list(pu.context.layer_sizes),
+                "timing": f"device events around blocks of calls, sides alternated, >= "
+                          f"{args.seconds} s per side; median and min-max over block means"})
+
+    torch.manual_seed(0)
+    net_u = GraphSAGE(2, F, H, False, agg_func="MEAN", Unsupervised=True).to(dev).train()
+    net_s = GraphSAGE(2, F, H, False, agg_func="MEAN", Unsupervised=False,
+                      class_size=3).to(dev).train()
+    y_s = torch.randint(0, 3, (B,), device=dev, generator=gen)
+    y_u = pu.labels.to(torch.float32)
+
+    def step_s(tab, fused):
+        a = ps.forward_args(tab)
+
+        def fn():
+            graphsage.SAGE_TRAIN_FUSED = fused
+            net_s.zero_grad(set_to_none=True)
+            _, logits = net_s(*a, None, None, None, None, None)
+            Fn.cross_entropy(logits, y_s).backward()
+        return fn
+
+    def step_u(tab, fused):
+        a = pu.forward_args(tab)
+
+        def fn():
+            graphsage.SAGE_TRAIN_FUSED = fused
+            net_u.zero_grad(set_to_none=True)
+            _, score = net_u(*a)
+            Fn.binary_cross_entropy_with_logits(score.squeeze(1), y_u).backward()
+        return fn
+
+    for name, step, iters in (("supervised_step", step_s, 4), ("unsupervised_step", step_u, 1)):
+        t = alternate(torch, {"fp32_off": step(table, False), "fp32_on": step(table, True),
+                              "bf16_off": step(table16, False), "bf16_on": step(table16, True)},
+                      args.seconds, iters)
+        res[name] = compare(t)
+        # the same numbers? one step per side on the fp32 table, every weight gradient
+        net = net_s if step is step_s else net_u
+        grads = {}
+        for fused in (False, True):
+            step(table, fused)()
+            grads[fused] = {k_: p.grad.clone() for k_, p in net.named_parameters()}
+        res[name]["grad_max_abs_diff_over_max_abs"] = {
+            k_: float((grads[True][k_] - g).abs().max() / g.abs().max())
+            for k_, g in grads[False].items()}
+        print(json.dumps({name: res[name]}), flush=True)
+        write()
+    graphsage.SAGE_TRAIN_FUSED = True
+
+    # ---- the two new launches alone, at the second tower's layer-1 shape
+    tower = pu.context
+    cidx, idx = tower.center_maps[-1], tower.neigh_maps[-1]
+    n_prev = int(tower.layers[1].numel())
+    M, k = idx.shape
+    dbuf = torch.randn(M, 2 * F, device=dev, generator=gen)
+    tr = ops.sage_maps_transpose(cidx, idx, n_prev)
+    lens = tr.ptr[1:] - tr.ptr[:-1]
+    gathered = M * (k + 1) * F * 4
+
+    def parent():
+        return (graphsage._scatter_rows(dbuf[:, :F], cidx.reshape(-1, 1), n_prev, 1.0)
+                + graphsage._scatter_rows(dbuf[:, F:], idx, n_prev, 1.0 / k))
+    old, new = parent(), ops.sage_scatter_concat(dbuf, tr, n_prev)
+    agree = float((new - old).abs().max() / old.abs().max())
+    del old, new
+    t = alternate(torch, {
+        "sage_maps_transpose": lambda: ops.sage_maps_transpose(cidx, idx, n_prev, check=False),
+        "sage_scatter_concat": lambda: ops.sage_scatter_concat(dbuf, tr, n_prev),
+        "parent_two_scatter_rows": parent}, args.seconds, 4)
+    kern = {k_: summary(v) for k_, v in t.items()}
+    sc = kern["sage_scatter_concat"]
+    sc["bytes_gathered"] = gathered
+    sc["hbm_fraction"] = gathered / (sc["median_ms"] * 1e-3) / HBM_BYTES_PER_S
+    res["second_tower_layer1"] = {
+        "M": M, "k": k, "n_prev": n_prev, "slots": M * (k + 1),
+        "longest_list": int(lens.max()), "median_list": float(lens.float().median()),
+        "lists_split_into_chunks": int((lens > 256).sum()),
+        "scatter_vs_parent_max_abs_diff_over_max_abs": agree, **kern}
+    print(json.dumps({"second_tower_layer1": res["second_tower_layer1"]}), flush=True)
+    write()
+
+
+if __name__ == "__main__":
+    main()
