@@ -171,3 +171,18 @@ extern "C" int gnn_sage_gather_concat_live_f32(const float* table, int64_t ldt, 
   return sage_gather_concat_entry<float>(table, ldt, n_table, self_idx, idx, ldi, M, live, k, feat,
                                          mode, self_out, ld_self, out, ldo, err_flag, stream);
 }
+
+extern "C" int gnn_sage_gather_concat_arg_supported(int64_t feat, int64_t k) {
+  return sage_concat_arg_shape(feat, k);
+}
+
+extern "C" int gnn_sage_gather_concat_arg_f32(const float* table, int64_t ldt, int64_t n_table,
+                                              const int64_t* self_idx, const int64_t* idx,
+                                              int64_t ldi, int64_t M, int64_t k, int64_t feat,
+                                              float* self_out, int64_t ld_self, float* out,
+                                              int64_t ldo, uint8_t* arg, int64_t lda,
+                                              int32_t* err_flag, void* stream) {
+  return sage_gather_concat_arg_entry<float>(table, ldt, n_table, self_idx, idx, ldi, M, k, feat,
+                                             self_out, ld_self, out, ldo, arg, lda, err_flag,
+                                             stream);
+}

@@ -109,3 +109,14 @@ extern "C" int gnn_gather_rows_bf16_f32(const uint16_t* x, int64_t ldx, int64_t 
                        0, s, as_bf16(x), ldx, n_x, idx, n, feat, out, ldo, err_flag);
   return launch_status();
 }
+
+extern "C" int gnn_sage_gather_concat_arg_bf16(const uint16_t* table, int64_t ldt, int64_t n_table,
+                                               const int64_t* self_idx, const int64_t* idx,
+                                               int64_t ldi, int64_t M, int64_t k, int64_t feat,
+                                               float* self_out, int64_t ld_self, float* out,
+                                               int64_t ldo, uint8_t* arg, int64_t lda,
+                                               int32_t* err_flag, void* stream) {
+  return sage_gather_concat_arg_entry<bf16_t>(as_bf16(table), ldt, n_table, self_idx, idx, ldi, M,
+                                              k, feat, self_out, ld_self, out, ldo, arg, lda,
+                                              err_flag, stream);
+}

@@ -19,6 +19,12 @@
 //     per chunk writes a partial row, and a last pass adds the partial rows of a target in
 //     chunk order. No floating-point atomics anywhere; the integer atomics only hand out
 //     places in the chunk list, and no sum depends on the place it was given.
+//   gnn_sage_scatter_concat_maxpool_f32: the same three passes for the MAXPOOL layer
+//     (gnn_sage_gather_concat_arg_f32 / _bf16), whose aggregate half is
+//     buf[m, F + f] = X[idx[m, arg[m, f]], f]: a neighbour slot (m, j) contributes
+//     dBuf[m, F + f] where arg[m, f] == j and nothing elsewhere (a select, so a NaN or Inf
+//     gradient of a slot that did not win reaches nobody), unscaled. The kernels are the MEAN
+//     ones instantiated over SbMaskArgs; the MEAN instances take SbArgs as before.
 #include <cstring>  // rocprim's texture_cache_iterator calls host memset
 
 #include <rocprim/rocprim.hpp>
@@ -115,6 +121,59 @@ struct SbArgs {
   int32_t max_long, max_tasks;
 };
 
+// MAXPOOL: arg[m, f] (uint8, pitch lda) is the neighbour column whose row won feature f of row m
+struct SbMaskArgs : SbArgs {
+  const uint8_t* arg;
+  int64_t lda;
+};
+
+// The masked sum of sb_sum below: a centre slot adds its row, a neighbour slot (m, j) the
+// elements of dbuf[m, F:2F] whose arg byte is j. Each lane loads the 4 bytes of
+// arg[m, 4 sub : 4 sub + 4] beside its 16-B gradient load; the mask SELECTS (x or 0.f), it
+// never multiplies.
+__device__ __forceinline__ f4 sb_sum(const SbMaskArgs& a, int64_t b, int64_t e, int64_t step,
+                                     int F, int sub) {
+  f4 acc = vzero<4>();
+  const uint32_t m32 = static_cast<uint32_t>(a.M), k32 = static_cast<uint32_t>(a.k);
+  constexpr uint32_t kAll = 0x100;  // no byte equals it: a centre slot keeps every element
+  for (int64_t p = b; p < e; p += step * kSbU) {
+    f4 v[kSbU];
+    uint32_t win[kSbU], col[kSbU];
+#pragma unroll
+    for (int u = 0; u < kSbU; ++u) {
+      v[u] = vzero<4>();
+      win[u] = 0;
+      col[u] = kAll;
+      const int64_t q = p + u * step;
+      if (q < e) {
+        const uint32_t s = static_cast<uint32_t>(a.slot[q]);
+        if (s < static_cast<uint32_t>(a.n_slots)) {
+          const float* row;
+          if (s < m32) {
+            row = a.dbuf + static_cast<int64_t>(s) * a.ldd;
+          } else {
+            const uint32_t m = (s - m32) / k32;
+            row = a.dbuf + static_cast<int64_t>(m) * a.ldd + F;
+            col[u] = (s - m32) - m * k32;
+            win[u] = *reinterpret_cast<const uint32_t*>(a.arg + static_cast<int64_t>(m) * a.lda +
+                                                        4 * sub);
+          }
+          v[u] = vload<4>(row + 4 * sub);
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kSbU; ++u) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const bool keep = col[u] == kAll || ((win[u] >> (8 * i)) & 0xffu) == col[u];
+        vset(acc, i, vget(acc, i) + (keep ? vget(v[u], i) : 0.f));
+      }
+    }
+  }
+  return acc;
+}
+
 // The sum over the slots at positions b, b + step, ... < e of the sorted list, in that order,
 // by one lane group: lane `sub` holds floats [4 sub, 4 sub + 4) of the row; kSbU loads in flight.
 // A slot outside [0, n_slots) (no builder writes one) contributes nothing.
@@ -160,8 +219,8 @@ __device__ __forceinline__ void sb_range(const SbArgs& a, int64_t t, int64_t& b,
 // pass 1: one lane group per target. Lists of at most kSbChunk slots are summed and stored
 // (an empty list stores zeros: the kernel owns all of dx); a longer one is entered into the
 // chunk list and left to passes 2 and 3.
-template <int LPR>
-__global__ __launch_bounds__(kSbBlock) void sage_scatter_rows_kernel(SbArgs a) {
+template <int LPR, typename A = SbArgs>
+__global__ __launch_bounds__(kSbBlock) void sage_scatter_rows_kernel(A a) {
   constexpr int F = 4 * LPR;
   const int64_t t = (static_cast<int64_t>(blockIdx.x) * kSbBlock + threadIdx.x) / LPR;
   const int sub = threadIdx.x % LPR;
@@ -185,8 +244,8 @@ __global__ __launch_bounds__(kSbBlock) void sage_scatter_rows_kernel(SbArgs a) {
 
 // pass 2: one wavefront per chunk. Its 64 / LPR lane groups take the chunk's slots round robin
 // (each in ascending order), the group sums are added by xor-shuffles: a fixed tree.
-template <int LPR>
-__global__ __launch_bounds__(kSbBlock) void sage_scatter_chunks_kernel(SbArgs a) {
+template <int LPR, typename A = SbArgs>
+__global__ __launch_bounds__(kSbBlock) void sage_scatter_chunks_kernel(A a) {
   constexpr int F = 4 * LPR;
   constexpr int EPI = kWave / LPR;
   const int lane = threadIdx.x & (kWave - 1);
@@ -210,7 +269,8 @@ __global__ __launch_bounds__(kSbBlock) void sage_scatter_chunks_kernel(SbArgs a)
   }
 }
 
-// pass 3: one lane group per split target adds its partial rows in chunk order
+// pass 3: one lane group per split target adds its partial rows in chunk order (the partial
+// rows are already masked: MAXPOOL runs the same instance)
 template <int LPR>
 __global__ __launch_bounds__(kSbBlock) void sage_scatter_combine_kernel(SbArgs a) {
   constexpr int F = 4 * LPR;
@@ -238,22 +298,22 @@ __global__ __launch_bounds__(kSbBlock) void sage_scatter_combine_kernel(SbArgs a
   }
 }
 
-template <int LPR>
-static int launch_sage_scatter(const SbArgs& a, hipStream_t s) {
+template <int LPR, typename A>
+static int launch_sage_scatter(const A& a, hipStream_t s) {
   const int64_t blocks = (a.n_prev * LPR + kSbBlock - 1) / kSbBlock;
   if (blocks > 0x7fffffffLL) return GNN_E_UNSUPPORTED;
   hipError_t e = hipMemsetAsync(a.count, 0, 2 * sizeof(int32_t), s);
   if (e != hipSuccess) return static_cast<int>(e);
-  hipLaunchKernelGGL((sage_scatter_rows_kernel<LPR>), dim3(static_cast<unsigned>(blocks)),
+  hipLaunchKernelGGL((sage_scatter_rows_kernel<LPR, A>), dim3(static_cast<unsigned>(blocks)),
                      dim3(kSbBlock), 0, s, a);
   int64_t g = (static_cast<int64_t>(a.max_tasks) + kSbWaves - 1) / kSbWaves;
   g = g < kSbGrid ? g : kSbGrid;
-  hipLaunchKernelGGL((sage_scatter_chunks_kernel<LPR>), dim3(static_cast<unsigned>(g)),
+  hipLaunchKernelGGL((sage_scatter_chunks_kernel<LPR, A>), dim3(static_cast<unsigned>(g)),
                      dim3(kSbBlock), 0, s, a);
   g = (static_cast<int64_t>(a.max_long) * LPR + kSbBlock - 1) / kSbBlock;
   g = g < kSbGrid ? g : kSbGrid;
   hipLaunchKernelGGL((sage_scatter_combine_kernel<LPR>), dim3(static_cast<unsigned>(g)),
-                     dim3(kSbBlock), 0, s, a);
+                     dim3(kSbBlock), 0, s, static_cast<const SbArgs&>(a));
   return launch_status();
 }
 
@@ -327,6 +387,56 @@ extern "C" int64_t gnn_sage_scatter_concat_workspace_bytes(int64_t M, int64_t k,
   return sb_layout(n, feat).bytes;
 }
 
+template <typename A>
+static int dispatch_sage_scatter(const A& a, int64_t feat, hipStream_t s) {
+  switch (feat / 4) {
+    case 1: return launch_sage_scatter<1>(a, s);
+    case 2: return launch_sage_scatter<2>(a, s);
+    case 4: return launch_sage_scatter<4>(a, s);
+    case 8: return launch_sage_scatter<8>(a, s);
+    case 16: return launch_sage_scatter<16>(a, s);
+    case 32: return launch_sage_scatter<32>(a, s);
+    default: return launch_sage_scatter<64>(a, s);
+  }
+}
+
+extern "C" int64_t gnn_sage_scatter_concat_maxpool_workspace_bytes(int64_t M, int64_t k,
+                                                                   int64_t feat) {
+  if (M < 0 || k < 0 || feat < 0) return GNN_E_ARG;
+  if (k < 1 || k > 255) return GNN_E_UNSUPPORTED;
+  return gnn_sage_scatter_concat_workspace_bytes(M, k, feat);  // the MEAN scatter's layout
+}
+
+extern "C" int gnn_sage_scatter_concat_maxpool_f32(const float* dbuf, int64_t ldd,
+                                                   const uint8_t* arg, int64_t lda,
+                                                   const int64_t* ptr, const int32_t* slot,
+                                                   int64_t M, int64_t k, int64_t feat,
+                                                   int64_t n_prev, float* dx, int64_t ldx,
+                                                   void* workspace, int64_t workspace_bytes,
+                                                   void* stream) {
+  if (M < 0 || k < 0 || feat < 0 || n_prev < 0) return GNN_E_ARG;
+  if (!ptr || !workspace || (n_prev > 0 && !dx) || (M > 0 && (!dbuf || !slot || !arg)))
+    return GNN_E_ARG;
+  const int64_t n = sb_slots(M, k);
+  if (n < 0 || n_prev >= 0x7fffffffLL || !gnn_sage_scatter_concat_supported(feat) || k < 1 ||
+      k > 255)
+    return GNN_E_UNSUPPORTED;
+  if (ldd < 2 * feat || ldx < feat || lda < feat) return GNN_E_ARG;
+  const SbLayout l = sb_layout(n, feat);
+  if (workspace_bytes < l.bytes) return GNN_E_ARG;
+  if (ldd % 4 || ldx % 4 || lda % 4 || !aligned_to(dbuf, 16) || !aligned_to(dx, 16) ||
+      !aligned_to(arg, 4) || !aligned_to(workspace, 16))
+    return GNN_E_ALIGN;
+  if (n_prev == 0) return GNN_OK;
+  char* w = static_cast<char*>(workspace);
+  SbMaskArgs a{{dbuf, ldd, ptr, slot, M, k, n_prev, n, 1.f, dx, ldx, reinterpret_cast<int32_t*>(w),
+                reinterpret_cast<int2*>(w + l.off_longs), reinterpret_cast<int2*>(w + l.off_tasks),
+                reinterpret_cast<float*>(w + l.off_part), static_cast<int32_t>(l.max_long),
+                static_cast<int32_t>(l.max_tasks)},
+               arg, lda};
+  return dispatch_sage_scatter(a, feat, static_cast<hipStream_t>(stream));
+}
+
 extern "C" int gnn_sage_scatter_concat_f32(const float* dbuf, int64_t ldd, const int64_t* ptr,
                                            const int32_t* slot, int64_t M, int64_t k, int64_t feat,
                                            int64_t n_prev, float* dx, int64_t ldx, void* workspace,
@@ -348,14 +458,5 @@ extern "C" int gnn_sage_scatter_concat_f32(const float* dbuf, int64_t ldd, const
            ldx, reinterpret_cast<int32_t*>(w), reinterpret_cast<int2*>(w + l.off_longs),
            reinterpret_cast<int2*>(w + l.off_tasks), reinterpret_cast<float*>(w + l.off_part),
            static_cast<int32_t>(l.max_long), static_cast<int32_t>(l.max_tasks)};
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  switch (feat / 4) {
-    case 1: return launch_sage_scatter<1>(a, s);
-    case 2: return launch_sage_scatter<2>(a, s);
-    case 4: return launch_sage_scatter<4>(a, s);
-    case 8: return launch_sage_scatter<8>(a, s);
-    case 16: return launch_sage_scatter<16>(a, s);
-    case 32: return launch_sage_scatter<32>(a, s);
-    default: return launch_sage_scatter<64>(a, s);
-  }
+  return dispatch_sage_scatter(a, feat, static_cast<hipStream_t>(stream));
 }

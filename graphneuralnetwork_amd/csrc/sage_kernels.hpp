@@ -45,7 +45,13 @@ template <> struct SageElem<bf16_t> { static constexpr int kVec = 8, kU = GNN_SA
 
 // kArgmaxF: the argmax index stored as fp32 (exact below 2^24) -- what the SageLayer's
 // torch.cat([self_feats, argmax]) promotes it to (GraphSAGE/GraphSAGE.py:17, graph_utils.py:8)
-enum SageMode : int32_t { kMean = 0, kArgmax = 1, kSum = 2, kMaxPool = 3, kArgmaxF = 4 };
+// kMaxPoolArg (the training layer, GATHER + SELF form only; not a public mode number): the value
+// max-pool AND its winner -- the fp32 value at the slot that wins under `beats` into out, that
+// slot as a uint8 into arg_out (k <= 255). The slot is kArgmax's; the value is kMaxPool's up to
+// the sign of a zero and the payload of a NaN (nanmax keeps the LAST of equal values and any
+// NaN, this keeps the value AT the stored slot: the first of equal values, the first NaN).
+enum SageMode : int32_t { kMean = 0, kArgmax = 1, kSum = 2, kMaxPool = 3, kArgmaxF = 4,
+                          kMaxPoolArg = 5 };
 
 // torch.max's value rule: a NaN on either side wins, else the larger value
 __device__ __forceinline__ float nanmax(float a, float b) { return (a > b || a != a) ? a : b; }
@@ -78,7 +84,10 @@ __global__ __launch_bounds__(kSageBlock) void sage_aggregate_kernel(
     const int64_t* __restrict__ idx, int64_t ldi, int64_t M, int64_t k, int64_t feat,
     void* __restrict__ out, int64_t ldo, int32_t* __restrict__ err,
     const int64_t* __restrict__ self_idx = nullptr, float* __restrict__ self_out = nullptr,
-    int64_t ld_self = 0, const int64_t* __restrict__ live = nullptr) {
+    int64_t ld_self = 0, const int64_t* __restrict__ live = nullptr,
+    uint8_t* __restrict__ arg_out = nullptr, int64_t lda = 0) {
+  static_assert(MODE != kMaxPoolArg || (GATHER && SELF && NCH == 1 && VW % 4 == 0),
+                "the winner-recording mode exists in the GATHER + SELF vector form only");
   typedef Row<T, VW> RX;
   constexpr int EPI = kWave / LPR;
   const int lane = threadIdx.x & (kWave - 1);
@@ -203,6 +212,20 @@ __global__ __launch_bounds__(kSageBlock) void sage_aggregate_kernel(
       // torch.mean: sum / k;  torch.sum: the sum;  torch.max(...).values: the max
       typename Vec<VW>::T r = MODE == kMean ? acc[ch] / static_cast<float>(k) : acc[ch];
       vstore<VW>(static_cast<float*>(out) + m * ldo + f, r);
+      if constexpr (MODE == kMaxPoolArg) {
+        // the lane that stored VW values stores their VW winners: 4 bytes per store (no slot
+        // was in range: the byte is 0)
+        uint32_t* ao = reinterpret_cast<uint32_t*>(arg_out + m * lda + f);
+#pragma unroll
+        for (int i = 0; i < VW; i += 4) {
+          uint32_t w = 0;
+#pragma unroll
+          for (int b = 0; b < 4; ++b)
+            w |= (arg[ch][i + b] == 0x7fffffff ? 0u : static_cast<uint32_t>(arg[ch][i + b]) & 0xffu)
+                 << (8 * b);
+          ao[i / 4] = w;
+        }
+      }
     } else {
       int64_t* o = static_cast<int64_t*>(out) + m * ldo + f;
       if constexpr (VW == 8) {  // a lane's 8 indices: four 16-B stores of two int64 each
@@ -233,6 +256,8 @@ struct SageArgsT {
   float* self_out = nullptr;          // ... into self_out[m] (one launch for cat[self, agg])
   int64_t ld_self = 0;
   const int64_t* live = nullptr;      // rows [0, min(*live, M)) only (device row count)
+  uint8_t* arg = nullptr;             // kMaxPoolArg: the winning slot of every out[m, f]
+  int64_t lda = 0;
 };
 typedef SageArgsT<> SageArgs;
 
@@ -306,6 +331,20 @@ static int run_sage(SageArgsT<T> a, int32_t mode, bool vec) {
   return GNN_OK;
 }
 
+// kMaxPoolArg: feat a power of two, one column chunk per lane (feat / kVec <= 64 lanes)
+template <int LPR, typename T>
+static int launch_sage_arg(const SageArgsT<T>& a) {
+  constexpr int VW = SageElem<T>::kVec;
+  const int64_t blocks = (a.M + kSageWaves - 1) / kSageWaves;
+  if (blocks > 0x7fffffffLL) return GNN_E_UNSUPPORTED;
+  hipLaunchKernelGGL(
+      (sage_aggregate_kernel<T, VW, LPR, 1, kMaxPoolArg, true, SageElem<T>::kU, true>),
+      dim3(static_cast<unsigned>(blocks)), dim3(kSageBlock), GNN_SAGE_LDS_PAD, a.s, a.src, a.ld_row,
+      a.ld_m, a.n_table, a.idx, a.ldi, a.M, a.k, a.feat, a.out, a.ldo, a.err, a.self_idx,
+      a.self_out, a.ld_self, nullptr, a.arg, a.lda);
+  return launch_status();
+}
+
 // The vector path of T needs whole lanes per row (feat and every pitch of T a multiple of
 // kVec, the base 16-B aligned) and fp32 / int64 outputs as the fp32 kernel's: pitch % 4 == 0,
 // 16-B aligned fp32, 32-B aligned int64. Anything else runs one element per lane.
@@ -366,6 +405,45 @@ static int sage_gather_concat_entry(const T* table, int64_t ldt, int64_t n_table
   SageArgsT<T> a{table, ldt, 0, n_table, idx, ldi, M, k, feat, out, ldo, err_flag,
                  static_cast<hipStream_t>(stream), self_idx, self_out, ld_self, live};
   return run_sage<true>(a, mode, vec);
+}
+
+// feat a power of two in [4, 256] and 1 <= k <= 255 (the slot fits a byte)
+static bool sage_concat_arg_shape(int64_t feat, int64_t k) {
+  return feat >= 4 && feat <= 256 && (feat & (feat - 1)) == 0 && k >= 1 && k <= 255;
+}
+
+// gnn_sage_gather_concat_arg_{f32,bf16}: MAXPOOL's cat[self, agg] plus the winning slot of every
+// (row, feature) as a uint8. The vector path only: a row is whole 16-B lanes of T (so a bf16
+// table needs feat >= 8: GNN_E_UNSUPPORTED), every pitch a multiple of its vector, arg in 4-B
+// words (GNN_E_ALIGN otherwise).
+template <typename T>
+static int sage_gather_concat_arg_entry(const T* table, int64_t ldt, int64_t n_table,
+                                        const int64_t* self_idx, const int64_t* idx, int64_t ldi,
+                                        int64_t M, int64_t k, int64_t feat, float* self_out,
+                                        int64_t ld_self, float* out, int64_t ldo, uint8_t* arg,
+                                        int64_t lda, int32_t* err_flag, void* stream) {
+  constexpr int VX = SageElem<T>::kVec;
+  if (M < 0 || k < 0 || feat < 0 || n_table < 0) return GNN_E_ARG;
+  if (!table || !self_idx || !idx || !self_out || !out || !arg || !err_flag) return GNN_E_ARG;
+  if (!sage_concat_arg_shape(feat, k) || feat % VX != 0) return GNN_E_UNSUPPORTED;
+  if (ldt < feat || ldo < feat || ld_self < feat || lda < feat || ldi < k) return GNN_E_ARG;
+  if (ldt % VX || ldo % 4 || ld_self % 4 || lda % 4 || !aligned_to(table, 16) ||
+      !aligned_to(out, 16) || !aligned_to(self_out, 16) || !aligned_to(arg, 4))
+    return GNN_E_ALIGN;
+  if (M == 0) return GNN_OK;
+  SageArgsT<T> a{table, ldt, 0, n_table, idx, ldi, M, k, feat, out, ldo, err_flag,
+                 static_cast<hipStream_t>(stream), self_idx, self_out, ld_self, nullptr, arg, lda};
+  switch (feat / VX) {
+    case 1: return launch_sage_arg<1>(a);
+    case 2: return launch_sage_arg<2>(a);
+    case 4: return launch_sage_arg<4>(a);
+    case 8: return launch_sage_arg<8>(a);
+    case 16: return launch_sage_arg<16>(a);
+    case 32: return launch_sage_arg<32>(a);
+    default:
+      if constexpr (VX == 4) return launch_sage_arg<64>(a);  // feat = 256 in fp32
+      return GNN_E_UNSUPPORTED;
+  }
 }
 
 }  // namespace gnn

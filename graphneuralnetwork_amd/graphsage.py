@@ -17,7 +17,9 @@ Hot path on gfx950:
 * training on the device sampler's batches (``l.backward()``, train_eval.py:112-119) -> one
   autograd function per MEAN layer (``_SageTrainLayerFn``): the inference launches forward,
   the weight gradient in one masked pass and the concat gather's adjoint on the device
-  (``csrc/sage_bwd.hip``) backward.
+  (``csrc/sage_bwd.hip``) backward; per MAXPOOL layer ``_SageMaxPoolTrainLayerFn``: the concat
+  gather records the winning neighbour as one byte per (row, feature), the adjoint sums the
+  gradient through that mask in a fixed order (no ``index_put_``, no float atomics).
 """
 from __future__ import annotations
 
@@ -30,8 +32,9 @@ from torch import nn
 from .graph import from_coo
 from .ops import (_bf16_inference_only, _masked_grad, _transform_or_mm, gather_rows,
                   gcn_transform, gemm_tn_masked, linear_relu_classify, sage_aggregate,
-                  sage_gather_aggregate, sage_gather_concat, sage_layer, sage_maps_transpose,
-                  sage_scatter_concat, sage_train_layer_supported, spmm_forward)
+                  sage_gather_aggregate, sage_gather_concat, sage_gather_concat_arg, sage_layer,
+                  sage_maps_transpose, sage_scatter_concat, sage_scatter_concat_maxpool,
+                  sage_train_layer_supported, spmm_forward)
 
 # the inference SageLayer GEMM relu([self | agg] @ W^T) runs on the hand-written MFMA kernel
 # (gnn_linear_relu_f32). With the split-bf16 arithmetic (the default, ops.set_transform_precision)
@@ -396,18 +399,87 @@ class _SageTrainLayerFn(torch.autograd.Function):
         return d_table, dW, None, None
 
 
-def _sage_train_layer(block, center: Gathered, neigh: Gathered):
+# The same for agg_func 'MAXPOOL' (``_SageMaxPoolTrainLayerFn``). False: the separate row gather,
+# the argmax and the value launches of ``_GatherMaxPoolAgg`` with its index_put_ backward, and
+# torch linear + addmm + relu (tools/sage_train_ab.py --agg MAXPOOL times both in one process).
+SAGE_TRAIN_FUSED_MAXPOOL = True
+
+
+def _maxpool_scatter_torch(dbuf, arg, cidx, idx, n_prev):
+    """The masked sum of ``sage_scatter_concat_maxpool`` in torch, for a shape it declines:
+    the centre rows by index_add_, each (row, feature) of the aggregate half onto the table row
+    of its winner by index_put_ (float atomics: the order of the sums is not fixed)."""
+    n = dbuf.shape[1] // 2
+    out = torch.zeros((n_prev, n), dtype=dbuf.dtype, device=dbuf.device)
+    out.index_add_(0, cidx, dbuf[:, :n])
+    rows = idx.gather(1, arg.to(torch.int64))                     # [M, F] table rows
+    cols = torch.arange(n, device=dbuf.device).expand_as(rows)
+    return out.index_put_((rows, cols), dbuf[:, n:], accumulate=True)
+
+
+class _SageMaxPoolTrainLayerFn(torch.autograd.Function):
+    """relu(W . cat[table[cidx], max_j table[idx[:, j]]]) (GraphSAGE/GraphSAGE.py:17-20 over the
+    gathers of :47-49, the aggregate torch.max(neigh, dim=1).values) with autograd w.r.t. W and,
+    where it asks for it, the fp32 table.
+
+    Forward: ``sage_gather_concat_arg`` writes buf = [self | max-pool] and the winning neighbour
+    column of every (row, feature) as a uint8 (the first maximum, a NaN first: torch's rule),
+    ``gcn_transform`` gives y = relu(buf W^T). Backward as ``_SageTrainLayerFn``: dW in one
+    masked pass; only for a table that requires grad dBuf = dY' W and dX =
+    ``sage_scatter_concat_maxpool`` over the device-built transposed maps: each neighbour slot
+    adds the gradient elements it won, in slot order -- no [n_prev, F] zero table, no [M, F]
+    int64 row ids, no index_put_, no float atomics."""
+
+    @staticmethod
+    def forward(ctx, table, W, cidx, idx):
+        r = sage_gather_concat_arg(table, cidx, idx, check=False)
+        if r is None:  # sage_train_layer_supported said the gather takes the shape
+            raise RuntimeError("the max-pool concat gather refused a shape it reports as covered")
+        buf, arg = r
+        y = gcn_transform(buf, W, relu=True)
+        if y is None:
+            raise RuntimeError("the SageLayer transform refused a shape it reports as covered")
+        ctx.save_for_backward(buf, y, W, cidx, idx, arg)
+        ctx.n_prev = table.shape[0]
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        buf, y, W, cidx, idx, arg = ctx.saved_tensors
+        d_table = dW = g = None
+        if ctx.needs_input_grad[1]:
+            r = gemm_tn_masked(buf, dy, y, 1.0, False, trans=True)
+            if r is not None:
+                dW = r[0]
+            else:
+                g = _masked_grad(dy, y, 1.0)
+                dW = torch.mm(g.t(), buf)
+        if ctx.needs_input_grad[0]:
+            if g is None:
+                g = _masked_grad(dy, y, 1.0)
+            dbuf = _transform_or_mm(g, W.t().contiguous())
+            tr = sage_maps_transpose(cidx, idx, ctx.n_prev, check=False)
+            if tr is not None:
+                d_table = sage_scatter_concat_maxpool(dbuf, arg, tr, ctx.n_prev)
+            if d_table is None:  # a shape the kernel declines
+                d_table = _maxpool_scatter_torch(dbuf, arg, cidx, idx, ctx.n_prev)
+        return d_table, dW, None, None
+
+
+def _sage_train_layer(block, center: Gathered, neigh: Gathered, agg: str = 'MEAN'):
     """The training SageLayer on trusted maps over one table, or None where
-    ``_SageTrainLayerFn`` does not cover the layer (the caller takes the unfused path)."""
+    ``_SageTrainLayerFn`` / ``_SageMaxPoolTrainLayerFn`` does not cover the layer (the caller
+    takes the unfused path)."""
     table, W = neigh.table, block.weight.weight
     idx, cidx = neigh.index, center.index
     if (idx.dim() != 2 or idx.dtype != torch.int64 or cidx.dtype != torch.int64
             or cidx.numel() != idx.shape[0] or idx.shape[0] == 0
             or not (W.requires_grad or table.requires_grad)
             or (table.dtype == torch.bfloat16 and table.requires_grad)  # raises as before
-            or not sage_train_layer_supported(table, W, idx.shape[1])):
+            or not sage_train_layer_supported(table, W, idx.shape[1], agg)):
         return None
-    return _SageTrainLayerFn.apply(table, W, cidx, idx)
+    fn = _SageMaxPoolTrainLayerFn if agg == 'MAXPOOL' else _SageTrainLayerFn
+    return fn.apply(table, W, cidx, idx)
 
 
 class GraphSAGE(nn.Module):
@@ -439,10 +511,12 @@ class GraphSAGE(nn.Module):
                 and neigh.table.dtype in (torch.float32, torch.bfloat16))
 
     def _train_fused_ok(self, block, center, neigh) -> bool:
-        """The training layer (``_SageTrainLayerFn``): MEAN over cat[self, agg], centre and
-        neighbours Gathered over ONE table through the device sampler's (trusted) maps."""
-        return (SAGE_TRAIN_FUSED and torch.is_grad_enabled() and not block.gcn
-                and self.agg_func == 'MEAN' and isinstance(center, Gathered)
+        """The training layer (``_SageTrainLayerFn`` / ``_SageMaxPoolTrainLayerFn``): MEAN or
+        MAXPOOL over cat[self, agg], centre and neighbours Gathered over ONE table through the
+        device sampler's (trusted) maps."""
+        on = {'MEAN': SAGE_TRAIN_FUSED, 'MAXPOOL': SAGE_TRAIN_FUSED_MAXPOOL}.get(self.agg_func)
+        return (bool(on) and torch.is_grad_enabled() and not block.gcn
+                and isinstance(center, Gathered)
                 and isinstance(neigh, Gathered) and center.table is neigh.table
                 and center.trusted and neigh.trusted)
 
@@ -464,7 +538,7 @@ class GraphSAGE(nn.Module):
                     center, neigh = _trim(center), _trim(neigh)
                     feats_data = None
                     if self._train_fused_ok(block, center, neigh):
-                        feats_data = _sage_train_layer(block, center, neigh)
+                        feats_data = _sage_train_layer(block, center, neigh, self.agg_func)
                     if feats_data is None:
                         if isinstance(center, Gathered):
                             center = _gather(center.table, center.index, center.trusted)

@@ -1811,19 +1811,132 @@ def sage_scatter_concat(dbuf: torch.Tensor, tr: SageMapsT, n_prev: int,
     return dx
 
 
-def sage_train_layer_supported(table: torch.Tensor, weight: torch.Tensor, k: int) -> bool:
-    """Whether the training SageLayer (graphsage._SageTrainLayerFn) runs on its own kernels for
-    an [n, F] table, an [H, 2F] weight and k neighbours per row: ``gcn_transform`` takes
-    (2F, H) and ``sage_scatter_concat`` takes F."""
+def sage_gather_concat_arg(table: torch.Tensor, self_idx: torch.Tensor, idx: torch.Tensor,
+                           check: bool = True):
+    """``sage_gather_concat(table, self_idx, idx, 'MAXPOOL')`` that also records the winner
+    (gnn_sage_gather_concat_arg_f32 / _bf16): returns ``(buf, arg)`` -- buf float32 [M, 2F] =
+    cat[table[self_idx], max_j table[idx[:, j]]], arg uint8 [M, F] the neighbour column whose
+    row holds that maximum under torch.argmax's order (a NaN first, then the larger value, then
+    the smaller column: ``sage_gather_aggregate(table, idx, 'MAX')`` as bytes). buf[m, F + f]
+    is the value AT arg[m, f]; it compares equal to MAXPOOL's (the sign of a zero and the
+    payload of a NaN may differ). What the training layer saves for its backward: one byte per
+    (row, feature) instead of an int64. None where the kernel does not take the shape (F not a
+    power of two in [4, 256] -- [8, 256] for a bfloat16 table --, k outside [1, 255], a table
+    view whose rows are not 16-B lanes)."""
+    _f32_or_bf16(table, "table")
+    _require_device(table, self_idx, idx)
+    table = _rows_x(table, "table")
+    _bf16_inference_only(table, "sage_gather_concat_arg")
+    if idx.dim() != 2:
+        raise ValueError("idx must be [M, k]")
+    idx = idx.to(torch.int64)
+    if idx.stride(1) != 1:
+        idx = idx.contiguous()
+    self_idx = self_idx.to(torch.int64).contiguous().view(-1)
+    M, k = idx.shape
+    F = table.shape[1]
+    if self_idx.numel() != M:
+        raise ValueError("self_idx must hold one index per output row")
+    lib = _lib.load()
+    vec = 8 if _bf16(table) else 4
+    if (not lib.gnn_sage_gather_concat_arg_supported(F, k) or F % vec
+            or table.stride(0) % vec or table.data_ptr() % 16):
+        return None
+    buf = torch.empty((M, 2 * F), dtype=torch.float32, device=table.device)
+    arg = torch.empty((M, F), dtype=torch.uint8, device=table.device)
+    if M == 0:
+        return buf, arg
+    err = _err_flag(table.device, check)
+    fn, name = ((lib.gnn_sage_gather_concat_arg_bf16, "gnn_sage_gather_concat_arg_bf16")
+                if _bf16(table) else
+                (lib.gnn_sage_gather_concat_arg_f32, "gnn_sage_gather_concat_arg_f32"))
+    _lib.check(fn(
+        table.data_ptr(), table.stride(0), table.shape[0], self_idx.data_ptr(), idx.data_ptr(),
+        idx.stride(0), M, k, F, buf.data_ptr(), 2 * F, buf[:, F:].data_ptr(), 2 * F,
+        arg.data_ptr(), F, err.data_ptr(), _lib.stream_handle(table.device)), name)
+    if check:
+        _check_err(err, "sage_gather_concat_arg")
+    return buf, arg
+
+
+def sage_scatter_concat_maxpool(dbuf: torch.Tensor, arg: torch.Tensor, tr: SageMapsT,
+                                n_prev: int, out: torch.Tensor | None = None
+                                ) -> torch.Tensor | None:
+    """The adjoint of ``sage_gather_concat_arg`` (gnn_sage_scatter_concat_maxpool_f32):
+    dX[t, f] = sum of dbuf[s, f] over the centre slots s of t + sum over the neighbour slots
+    (m, j) of t of (dbuf[m, F + f] if arg[m, f] == j else 0), for the maps
+    ``tr = sage_maps_transpose(...)``. The mask selects (a non-finite gradient at a slot that
+    did not win reaches nobody), as torch's index_put_ of the gradient does. Everything else is
+    ``sage_scatter_concat``'s: fp32 sums in slot order, no float atomics, bit-identical from
+    run to run, every row of the result stored. ``arg``: a uint8 [M, F] view with unit column
+    stride and rows of whole 4-B words. None where the kernel does not take the shape (the
+    widths of ``sage_scatter_concat``, k outside [1, 255], a misaligned view)."""
+    _require_device(dbuf, arg, tr.ptr, tr.slot, out)
+    if dbuf.dtype != torch.float32:
+        raise TypeError(f"dbuf must be float32 (got {dbuf.dtype})")
+    if arg.dtype != torch.uint8:
+        raise TypeError(f"arg must be uint8 (got {arg.dtype})")
+    if dbuf.dim() != 2 or dbuf.shape[1] % 2:
+        raise ValueError("dbuf must be [M, 2F]")
+    n_prev = int(n_prev)
+    M, k = tr.M, tr.k
+    F = dbuf.shape[1] // 2
+    if (dbuf.shape[0] != M or tuple(arg.shape) != (M, F) or tr.ptr.numel() != n_prev + 1
+            or tr.slot.numel() != M * (k + 1)):
+        raise ValueError("dbuf, arg, the transposed maps and n_prev do not belong together")
+    if tr.ptr.dtype != torch.int64 or tr.slot.dtype != torch.int32:
+        raise TypeError("the transposed maps must be (int64 ptr, int32 slot)")
+    if out is not None and (out.shape != (n_prev, F) or out.dtype != torch.float32
+                            or not out.is_contiguous() or out.data_ptr() % 16):
+        raise ValueError(f"out must be a contiguous float32 [{n_prev}, {F}] tensor")
+    lib = _lib.load()
+    if k < 1 or k > 255 or not lib.gnn_sage_scatter_concat_supported(F):
+        return None
+    if M == 0:
+        return (torch.zeros((n_prev, F), dtype=torch.float32, device=dbuf.device)
+                if out is None else out.zero_())
+    if (dbuf.stride(1) != 1 or (M > 1 and (dbuf.stride(0) % 4 or dbuf.stride(0) < 2 * F))
+            or dbuf.data_ptr() % 16 or arg.stride(1) != 1 or arg.data_ptr() % 4
+            or (M > 1 and (arg.stride(0) % 4 or arg.stride(0) < F))):
+        return None
+    nbytes = int(lib.gnn_sage_scatter_concat_maxpool_workspace_bytes(M, k, F))
+    if nbytes < 0:
+        return None
+    dx = out if out is not None else torch.empty((n_prev, F), dtype=torch.float32,
+                                                 device=dbuf.device)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dbuf.device)
+    ptr, slot = tr.ptr.contiguous(), tr.slot.contiguous()
+    _lib.check(lib.gnn_sage_scatter_concat_maxpool_f32(
+        dbuf.data_ptr(), dbuf.stride(0) if M > 1 else 2 * F, arg.data_ptr(),
+        arg.stride(0) if M > 1 else F, ptr.data_ptr(), slot.data_ptr(), M, k, F, n_prev,
+        dx.data_ptr(), F, ws.data_ptr(), ws.numel(), _lib.stream_handle(dbuf.device)),
+        "gnn_sage_scatter_concat_maxpool_f32")
+    return dx
+
+
+def sage_train_layer_supported(table: torch.Tensor, weight: torch.Tensor, k: int,
+                               agg: str = 'MEAN') -> bool:
+    """Whether the training SageLayer (graphsage._SageTrainLayerFn; ``agg`` 'MAXPOOL':
+    graphsage._SageMaxPoolTrainLayerFn) runs on its own kernels for an [n, F] table, an [H, 2F]
+    weight and k neighbours per row: ``gcn_transform`` takes (2F, H) and ``sage_scatter_concat``
+    takes F; for 'MAXPOOL' also ``sage_gather_concat_arg`` takes (F, k) and the table's rows."""
+    if agg not in ('MEAN', 'MAXPOOL'):
+        return False
     if (not table.is_cuda or not weight.is_cuda or table.dim() != 2 or weight.dim() != 2
             or table.dtype not in (torch.float32, torch.bfloat16)
             or weight.dtype != torch.float32 or k < 1):
         return False
     F, (H, K) = table.shape[1], weight.shape
     lib = _lib.load()
-    return bool(K == 2 * F and lib.gnn_gcn_transform_supported(K, H)
-                and (TRANSFORM_WIDE_MFMA or not (H == 256 and K > 64))
-                and lib.gnn_sage_scatter_concat_supported(F))
+    ok = bool(K == 2 * F and lib.gnn_gcn_transform_supported(K, H)
+              and (TRANSFORM_WIDE_MFMA or not (H == 256 and K > 64))
+              and lib.gnn_sage_scatter_concat_supported(F))
+    if ok and agg == 'MAXPOOL':
+        vec = 8 if table.dtype == torch.bfloat16 else 4
+        ok = bool(lib.gnn_sage_gather_concat_arg_supported(F, k) and F % vec == 0
+                  and table.stride(1) == 1 and table.stride(0) % vec == 0
+                  and table.data_ptr() % 16 == 0)
+    return ok
 
 
 # The fused layer is opt-in (set SAGE_FUSED_MIN_ROWS to the smallest frontier to fuse): at

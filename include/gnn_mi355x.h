@@ -965,6 +965,59 @@ int gnn_sage_scatter_concat_f32(const float* dbuf, int64_t ldd, const int64_t* p
                                 int64_t workspace_bytes, void* stream);
 
 /*
+ * The MAXPOOL training SageLayer: cat[self, max-pool] with the winner recorded, and its adjoint.
+ *
+ * gnn_sage_gather_concat_arg_f32 / _bf16 replace, in one launch, the torch.max(neigh_feat,
+ * dim=1) form of Aggregator (GraphSAGE/graph_utils.py:4-11: values AND indices, what autograd
+ * keeps for l.backward()) over the torch.embedding gathers of GraphSAGE/GraphSAGE.py:47-49, and
+ * the torch.cat of GraphSAGE.py:17. Arguments as gnn_sage_gather_concat_f32 / _bf16 without the
+ * mode, plus arg (uint8 [M, lda >= feat]):
+ *     self_out[m, :F] = table[self_idx[m]]                       (a bf16 row widened)
+ *     out[m, f]       = table[idx[m, arg[m, f]], f]              (the max over j, fp32)
+ *     arg[m, f]       = the slot j in [0, k) that wins under torch.argmax's order: a NaN first,
+ *                       then the larger value, then the smaller j -- what GNN_SAGE_ARGMAX gives.
+ *   out holds the value AT the stored slot, bit for bit. It compares equal to what
+ *   GNN_SAGE_MAXPOOL writes; the bits can differ in the sign of a zero (+0.0 ties -0.0: the
+ *   first wins here) and in the payload of a NaN (among several NaNs the first is stored).
+ *   An index outside [0, n_table) sets bit 0 of *err_flag and reads nothing; the arg bytes of
+ *   such a row are stored but unspecified.
+ *   gnn_sage_gather_concat_arg_supported(feat, k): feat a power of two in [4, 256] and
+ *   1 <= k <= 255 (the slot fits a byte); the bf16 entry also needs feat >= 8 (one lane loads
+ *   16 B = 8 bf16). Anything else: GNN_E_UNSUPPORTED. 16-B lanes only: table, self_out and out
+ *   16-B aligned, ldt a multiple of 4 (f32) / 8 (bf16), ld_self, ldo and lda multiples of 4, arg
+ *   4-B aligned (GNN_E_ALIGN). A null pointer, a negative size or a pitch below its row:
+ *   GNN_E_ARG. M == 0 -> GNN_OK.
+ * gnn_sage_scatter_concat_maxpool_f32 replaces what l.backward() does for those lines (the
+ * index_put_ / scatter_ of the gradient onto the winning rows, and the embedding backward of the
+ * centre rows). Arguments as gnn_sage_scatter_concat_f32 plus arg / lda as written above:
+ *     dx[t, f] = sum_{centre slots s of t} dbuf[s, f]
+ *              + sum_{neighbour slots (m, j) of t} (arg[m, f] == j ? dbuf[m, F + f] : 0)
+ *   over the maps of gnn_sage_maps_transpose. The mask selects: a NaN or Inf gradient at a slot
+ *   that did not win reaches no target. Order of summation, chunking, determinism, the stored
+ *   zero rows and the workspace layout are the MEAN scatter's
+ *   (gnn_sage_scatter_concat_maxpool_workspace_bytes(M, k, F)). Widths as
+ *   gnn_sage_scatter_concat_supported, and 1 <= k <= 255, else GNN_E_UNSUPPORTED; lda >= F
+ *   (GNN_E_ARG), lda a multiple of 4 and arg 4-B aligned (GNN_E_ALIGN).
+ */
+int gnn_sage_gather_concat_arg_supported(int64_t feat, int64_t k);
+int gnn_sage_gather_concat_arg_f32(const float* table, int64_t ldt, int64_t n_table,
+                                   const int64_t* self_idx, const int64_t* idx, int64_t ldi,
+                                   int64_t M, int64_t k, int64_t feat, float* self_out,
+                                   int64_t ld_self, float* out, int64_t ldo, uint8_t* arg,
+                                   int64_t lda, int32_t* err_flag, void* stream);
+int gnn_sage_gather_concat_arg_bf16(const uint16_t* table, int64_t ldt, int64_t n_table,
+                                    const int64_t* self_idx, const int64_t* idx, int64_t ldi,
+                                    int64_t M, int64_t k, int64_t feat, float* self_out,
+                                    int64_t ld_self, float* out, int64_t ldo, uint8_t* arg,
+                                    int64_t lda, int32_t* err_flag, void* stream);
+int64_t gnn_sage_scatter_concat_maxpool_workspace_bytes(int64_t M, int64_t k, int64_t feat);
+int gnn_sage_scatter_concat_maxpool_f32(const float* dbuf, int64_t ldd, const uint8_t* arg,
+                                        int64_t lda, const int64_t* ptr, const int32_t* slot,
+                                        int64_t M, int64_t k, int64_t feat, int64_t n_prev,
+                                        float* dx, int64_t ldx, void* workspace,
+                                        int64_t workspace_bytes, void* stream);
+
+/*
  * Hashed element dropout fused with a row gather, replacing F.dropout(x, p, training) at
  * GAT/models/GAT.py:15,17 in training (and its backward): r = idx ? idx[i] : i,
  * out[i, c] = x[r, c] / (1 - p) when the (seed, key, c) hash clears p (common.hpp

@@ -19,6 +19,14 @@ side at least --seconds of timed work, median and min-max of the block means:
     and beside them what they replace: the two ``_scatter_rows`` calls and the sum of their
     results (autograd's accumulation of the two gradients of one table).
 
+--agg MAXPOOL: the same protocol for the max-pool layer (graphsage._SageMaxPoolTrainLayerFn,
+switch graphsage.SAGE_TRAIN_FUSED_MAXPOOL; off: the row gather, the argmax and value launches of
+_GatherMaxPoolAgg and its index_put_ backward). The two new ops alone, at the same layer-1 shape
+over a random fp32 table: ``sage_gather_concat_arg`` against the three launches it replaces, and
+``sage_scatter_concat_maxpool`` against the backward it replaces (the index_put_ of the aggregate
+half with its zero table, row-id and column tensors, the centre rows' ``_scatter_rows``, and
+their sum), plus the bytes each side keeps for the backward (uint8 against int64 winners).
+
 Each comparison also records that both sides compute the same numbers at this size: the largest
 difference of every weight gradient (one step per side) and of the scatter's output, over the
 largest magnitude of the previous path's.
@@ -58,10 +66,12 @@ def main():
     ap.add_argument("--feat", type=int, default=128)
     ap.add_argument("--seeds", type=int, default=8192)
     ap.add_argument("--seconds", type=float, default=1.0, help="timed work per side, at least")
+    ap.add_argument("--agg", choices=("MEAN", "MAXPOOL"), default="MEAN")
     ap.add_argument("--out", required=True)
     args = ap.parse_args()
     n, e = (1_000_000, 10_000_000) if args.small else (10_000_000, 100_000_000)
     res = {}
+    switch = "SAGE_TRAIN_FUSED" if args.agg == "MEAN" else "SAGE_TRAIN_FUSED_MAXPOOL"
 
     def write():
         Path(args.out).parent.mkdir(parents=True, exist_ok=True)
@@ -94,6 +104,8 @@ def main():
     pu = S.sample_unsupervised_batch(adj, seeds, fanouts, WINDOW, K, seed=1, contexts=ctx_b,
                                      negatives=neg_b)
     ps = S.sample_batch(adj, seeds, fanouts, seed=1)
+    if args.agg != "MEAN":
+        res.update({"agg": args.agg, "switch": f"graphsage.{switch}"})
     res.update({"workload": "cfg4" if not args.small else "small", "nodes": n, "edges": e,
                 "feat": F, "hidden": H, "seeds": B, "window": WINDOW, "K": K,
                 "fanout": list(fanouts), "device": torch.cuda.get_device_name(dev),
@@ -104,8 +116,8 @@ def main():
                           f"{args.seconds} s per side; median and min-max over block means"})
 
     torch.manual_seed(0)
-    net_u = GraphSAGE(2, F, H, False, agg_func="MEAN", Unsupervised=True).to(dev).train()
-    net_s = GraphSAGE(2, F, H, False, agg_func="MEAN", Unsupervised=False,
+    net_u = GraphSAGE(2, F, H, False, agg_func=args.agg, Unsupervised=True).to(dev).train()
+    net_s = GraphSAGE(2, F, H, False, agg_func=args.agg, Unsupervised=False,
                       class_size=3).to(dev).train()
     y_s = torch.randint(0, 3, (B,), device=dev, generator=gen)
     y_u = pu.labels.to(torch.float32)
@@ -114,7 +126,7 @@ def main():
         a = ps.forward_args(tab)
 
         def fn():
-            graphsage.SAGE_TRAIN_FUSED = fused
+            setattr(graphsage, switch, fused)
             net_s.zero_grad(set_to_none=True)
             _, logits = net_s(*a, None, None, None, None, None)
             Fn.cross_entropy(logits, y_s).backward()
@@ -124,7 +136,7 @@ def main():
         a = pu.forward_args(tab)
 
         def fn():
-            graphsage.SAGE_TRAIN_FUSED = fused
+            setattr(graphsage, switch, fused)
             net_u.zero_grad(set_to_none=True)
             _, score = net_u(*a)
             Fn.binary_cross_entropy_with_logits(score.squeeze(1), y_u).backward()
@@ -144,9 +156,30 @@ def main():
         res[name]["grad_max_abs_diff_over_max_abs"] = {
             k_: float((grads[True][k_] - g).abs().max() / g.abs().max())
             for k_, g in grads[False].items()}
+        if args.agg == "MAXPOOL" and step is step_s:
+            # the two sides run layer 0's GEMM on different kernels, and a maximum is not
+            # continuous: how many layer-1 winners land on another row because of that
+            with torch.no_grad():
+                W0 = net_s.sage_blocks.sage_layer0.weight.weight
+                buf, _ = ops.sage_gather_concat_arg(table, ps.frontier, ps.frontier_nbrs,
+                                                    check=False)
+                h_on = ops.gcn_transform(buf, W0, relu=True)
+                h_off = torch.relu(torch.addmm(Fn.linear(buf[:, :F], W0[:, :F]), buf[:, F:],
+                                               W0[:, F:].t()))
+                nm = ps.neigh_maps[-1]
+                r_on = nm.gather(1, ops.sage_gather_aggregate(h_on, nm, "MAX", check=False))
+                r_off = nm.gather(1, ops.sage_gather_aggregate(h_off, nm, "MAX", check=False))
+                top = ops.sage_gather_aggregate(h_off, nm, "MAXPOOL", check=False)
+                res[name]["layer1_winners"] = {
+                    "entries": r_on.numel(),
+                    "on_another_row_with_a_positive_maximum":
+                        int(((r_on != r_off) & (top > 0)).sum()),
+                    "layer0_output_max_abs_diff": float((h_on - h_off).abs().max()),
+                    "layer0_output_max_abs": float(h_off.abs().max())}
+                del buf, h_on, h_off, r_on, r_off, top
         print(json.dumps({name: res[name]}), flush=True)
         write()
-    graphsage.SAGE_TRAIN_FUSED = True
+    setattr(graphsage, switch, True)
 
     # ---- the two new launches alone, at the second tower's layer-1 shape
     tower = pu.context
@@ -157,6 +190,55 @@ def main():
     tr = ops.sage_maps_transpose(cidx, idx, n_prev)
     lens = tr.ptr[1:] - tr.ptr[:-1]
     gathered = M * (k + 1) * F * 4
+    if args.agg == "MAXPOOL":
+        h = torch.randn(n_prev, F, device=dev, generator=gen)  # layer 0's output stands in
+
+        def fwd_parent():
+            c = ops.gather_rows(h, cidx, check=False)
+            a = ops.sage_gather_aggregate(h, idx, "MAX", check=False)
+            return c, a, ops.sage_gather_aggregate(h, idx, "MAXPOOL", check=False)
+
+        def bwd_parent():  # _GatherMaxPoolAgg.backward + _GatherRows.backward + their sum
+            rows = idx.gather(1, arg64)
+            cols = torch.arange(F, device=dev).expand_as(rows)
+            out = torch.zeros((n_prev, F), device=dev)
+            out.index_put_((rows, cols), dbuf[:, F:], accumulate=True)
+            return out + graphsage._scatter_rows(dbuf[:, :F], cidx.reshape(-1, 1), n_prev, 1.0)
+        buf, arg = ops.sage_gather_concat_arg(h, cidx, idx, check=False)
+        c_, arg64, v_ = fwd_parent()
+        fwd_same = bool(torch.equal(buf[:, :F], c_) and torch.equal(buf[:, F:], v_)
+                        and torch.equal(arg.to(torch.int64), arg64))
+        old, new = bwd_parent(), ops.sage_scatter_concat_maxpool(dbuf, arg, tr, n_prev)
+        agree = float((new - old).abs().max() / old.abs().max())
+        again = ops.sage_scatter_concat_maxpool(dbuf, arg, tr, n_prev)
+        rerun = {"sage_scatter_concat_maxpool": bool(torch.equal(new, again)),
+                 "parent_index_put": bool(torch.equal(old, bwd_parent()))}
+        del old, new, again, c_, v_, buf
+        t = alternate(torch, {
+            "sage_gather_concat_arg": lambda: ops.sage_gather_concat_arg(h, cidx, idx, check=False),
+            "parent_gather_argmax_maxpool": fwd_parent,
+            "sage_scatter_concat_maxpool":
+                lambda: ops.sage_scatter_concat_maxpool(dbuf, arg, tr, n_prev),
+            "parent_index_put_backward": bwd_parent}, args.seconds, 4)
+        kern = {k_: summary(v) for k_, v in t.items()}
+        sc = kern["sage_scatter_concat_maxpool"]
+        sc["bytes_gathered"] = gathered + M * (k + 1) * F  # the gradient rows and their winners
+        sc["hbm_fraction"] = sc["bytes_gathered"] / (sc["median_ms"] * 1e-3) / HBM_BYTES_PER_S
+        res["second_tower_layer1"] = {
+            "M": M, "k": k, "n_prev": n_prev, "slots": M * (k + 1),
+            "longest_list": int(lens.max()), "lists_split_into_chunks": int((lens > 256).sum()),
+            "forward_bit_identical_to_parent_launches": fwd_same,
+            "scatter_vs_parent_max_abs_diff_over_max_abs": agree,
+            "bit_identical_on_rerun": rerun,
+            "saved_winner_bytes": {"uint8_arg": M * F, "parent_int64_argmax": M * F * 8},
+            **kern}
+        l0 = int(tower.layers[-1].numel())  # the second tower's layer-0 rows
+        res["second_tower_layer0_saved_winner_bytes"] = {
+            "M": l0, "uint8_arg": l0 * F, "parent_int64_argmax": l0 * F * 8,
+            "note": "from the shape; only a table that requires grad saves it in the parent"}
+        print(json.dumps({"second_tower_layer1": res["second_tower_layer1"]}), flush=True)
+        write()
+        return
 
     def parent():
         return (graphsage._scatter_rows(dbuf[:, :F], cidx.reshape(-1, 1), n_prev, 1.0)
