@@ -125,6 +125,26 @@ SIGNATURES: dict[str, tuple] = {
     "gnn_sage_scatter_concat_maxpool_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64,
                                                             _i64, _i64, _i64, _vp, _i64, _vp, _i64,
                                                             _vp]),
+    # the gcn-mode SageLayer: the aggregate alone (live rows, winner recorded), its adjoint
+    "gnn_sage_gather_aggregate_live_f32": (ctypes.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp,
+                                                           _i64, _i64, _i32, _vp, _i64, _vp, _vp]),
+    "gnn_sage_gather_aggregate_live_bf16": (ctypes.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp,
+                                                            _i64, _i64, _i32, _vp, _i64, _vp, _vp]),
+    "gnn_sage_gather_aggregate_arg_supported": (ctypes.c_int, [_i64, _i64]),
+    "gnn_sage_gather_aggregate_arg_f32": (ctypes.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i64,
+                                                          _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "gnn_sage_gather_aggregate_arg_bf16": (ctypes.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i64,
+                                                           _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "gnn_sage_maps_transpose_nbr_workspace_bytes": (_i64, [_i64, _i64]),
+    "gnn_sage_maps_transpose_nbr": (ctypes.c_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp,
+                                                   _vp, _i64, _vp]),
+    "gnn_sage_scatter_agg_workspace_bytes": (_i64, [_i64, _i64, _i64]),
+    "gnn_sage_scatter_agg_f32": (ctypes.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64,
+                                                _vp, _i64, _vp, _i64, _vp]),
+    "gnn_sage_scatter_agg_maxpool_workspace_bytes": (_i64, [_i64, _i64, _i64]),
+    "gnn_sage_scatter_agg_maxpool_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64,
+                                                        _i64, _i64, _i64, _vp, _i64, _vp, _i64,
+                                                        _vp]),
     "gnn_halo_alltoallv_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
     "gnn_halo_rccl_path": (ctypes.c_int, [ctypes.c_char_p, _i64]),
     "gnn_spmm_plan_scratch_bytes": (_i64, [_i64]),

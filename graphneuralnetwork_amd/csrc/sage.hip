@@ -186,3 +186,26 @@ extern "C" int gnn_sage_gather_concat_arg_f32(const float* table, int64_t ldt, i
                                              self_out, ld_self, out, ldo, arg, lda, err_flag,
                                              stream);
 }
+
+// ---- the gcn-mode SageLayer (GraphSAGE/GraphSAGE.py:13-14: Linear over the aggregate alone) ----
+extern "C" int gnn_sage_gather_aggregate_live_f32(const float* table, int64_t ldt, int64_t n_table,
+                                                  const int64_t* idx, int64_t ldi, int64_t M,
+                                                  const int64_t* live, int64_t k, int64_t feat,
+                                                  int32_t mode, float* out, int64_t ldo,
+                                                  int32_t* err_flag, void* stream) {
+  return sage_gather_aggregate_live_entry<float>(table, ldt, n_table, idx, ldi, M, live, k, feat,
+                                                 mode, out, ldo, err_flag, stream);
+}
+
+extern "C" int gnn_sage_gather_aggregate_arg_supported(int64_t feat, int64_t k) {
+  return sage_concat_arg_shape(feat, k);
+}
+
+extern "C" int gnn_sage_gather_aggregate_arg_f32(const float* table, int64_t ldt, int64_t n_table,
+                                                 const int64_t* idx, int64_t ldi, int64_t M,
+                                                 int64_t k, int64_t feat, float* out, int64_t ldo,
+                                                 uint8_t* arg, int64_t lda, int32_t* err_flag,
+                                                 void* stream) {
+  return sage_gather_aggregate_arg_entry<float>(table, ldt, n_table, idx, ldi, M, k, feat, out, ldo,
+                                                arg, lda, err_flag, stream);
+}

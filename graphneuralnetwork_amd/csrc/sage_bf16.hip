@@ -120,3 +120,22 @@ extern "C" int gnn_sage_gather_concat_arg_bf16(const uint16_t* table, int64_t ld
                                               k, feat, self_out, ld_self, out, ldo, arg, lda,
                                               err_flag, stream);
 }
+
+extern "C" int gnn_sage_gather_aggregate_live_bf16(const uint16_t* table, int64_t ldt,
+                                                   int64_t n_table, const int64_t* idx,
+                                                   int64_t ldi, int64_t M, const int64_t* live,
+                                                   int64_t k, int64_t feat, int32_t mode,
+                                                   float* out, int64_t ldo, int32_t* err_flag,
+                                                   void* stream) {
+  return sage_gather_aggregate_live_entry<bf16_t>(as_bf16(table), ldt, n_table, idx, ldi, M, live,
+                                                  k, feat, mode, out, ldo, err_flag, stream);
+}
+
+extern "C" int gnn_sage_gather_aggregate_arg_bf16(const uint16_t* table, int64_t ldt,
+                                                  int64_t n_table, const int64_t* idx, int64_t ldi,
+                                                  int64_t M, int64_t k, int64_t feat, float* out,
+                                                  int64_t ldo, uint8_t* arg, int64_t lda,
+                                                  int32_t* err_flag, void* stream) {
+  return sage_gather_aggregate_arg_entry<bf16_t>(as_bf16(table), ldt, n_table, idx, ldi, M, k, feat,
+                                                 out, ldo, arg, lda, err_flag, stream);
+}

@@ -25,6 +25,10 @@
 //     dBuf[m, F + f] where arg[m, f] == j and nothing elsewhere (a select, so a NaN or Inf
 //     gradient of a slot that did not win reaches nobody), unscaled. The kernels are the MEAN
 //     ones instantiated over SbMaskArgs; the MEAN instances take SbArgs as before.
+//   gnn_sage_maps_transpose_nbr, gnn_sage_scatter_agg_f32 / _maxpool_f32: the same for the
+//     gcn-mode layer (GraphSAGE/GraphSAGE.py:13-14: buf[m] = agg_j X[idx[m, j]], no centre half):
+//     M k slots, slot e the entry (e / k, e % k), dBuf [M, F]. The slot decoding is a property of
+//     the argument struct (SbAggArgs / SbAggMaskArgs); the passes are the ones above.
 #include <cstring>  // rocprim's texture_cache_iterator calls host memset
 
 #include <rocprim/rocprim.hpp>
@@ -53,6 +57,12 @@ static int64_t sb_slots(int64_t M, int64_t k) {
   return M * (k + 1);
 }
 
+// the gcn-mode layer has no centre half: M k slots, slot e is entry (e / k, e % k)
+static int64_t sb_slots_nbr(int64_t M, int64_t k) {
+  if (k > 0 && M > 0x7fffffffLL / k) return -1;
+  return M * k;
+}
+
 static unsigned sb_key_bits(int64_t n_prev) {  // keys are targets in [0, n_prev]
   unsigned b = 1;
   while (b < 32 && (1LL << b) <= n_prev) ++b;
@@ -69,18 +79,20 @@ static size_t sb_sort_temp(int64_t n, unsigned bits) {
 }
 
 // keys[s] = the target of slot s; an index outside [0, n_prev) raises the flag and sorts last
-// (key n_prev), past ptr[n_prev]: the scatter never reads its slot
+// (key n_prev), past ptr[n_prev]: the scatter never reads its slot.
+// CENTRE: the M centre slots come first (the concat layer); off: the neighbour map alone
+template <bool CENTRE>
 __global__ __launch_bounds__(kSbBlock) void sage_slot_keys_kernel(
     const int64_t* __restrict__ cidx, const int64_t* __restrict__ idx, int64_t ldi, int64_t M,
     int64_t k, int64_t n_prev, uint32_t* __restrict__ keys, int32_t* __restrict__ err) {
-  const int64_t n = M * (k + 1);
+  const int64_t n = M * (CENTRE ? k + 1 : k);
   const int64_t step = static_cast<int64_t>(gridDim.x) * kSbBlock;
   for (int64_t s = static_cast<int64_t>(blockIdx.x) * kSbBlock + threadIdx.x; s < n; s += step) {
     int64_t t;
-    if (s < M) {
+    if (CENTRE && s < M) {
       t = cidx[s];
     } else {
-      const uint32_t e = static_cast<uint32_t>(s - M), kk = static_cast<uint32_t>(k);
+      const uint32_t e = static_cast<uint32_t>(CENTRE ? s - M : s), kk = static_cast<uint32_t>(k);
       t = idx[static_cast<int64_t>(e / kk) * ldi + e % kk];
     }
     if (t < 0 || t >= n_prev) {
@@ -119,20 +131,34 @@ struct SbArgs {
   int2* tasks;     // (target, chunk number) of every chunk
   float* part;     // one partial row per chunk
   int32_t max_long, max_tasks;
+  // how a slot is decoded. kCentre: slots [0, M) are centre rows (dbuf[s, 0:F], unscaled), the
+  // neighbour entries follow and read dbuf[m, F:2F]; off (the gcn-mode layer, SbAgg*Args):
+  // every slot is a neighbour entry e = (m, j) and reads dbuf[m, 0:F]. kMask: the MAXPOOL select
+  static constexpr bool kCentre = true, kMask = false;
 };
 
 // MAXPOOL: arg[m, f] (uint8, pitch lda) is the neighbour column whose row won feature f of row m
 struct SbMaskArgs : SbArgs {
   const uint8_t* arg;
   int64_t lda;
+  static constexpr bool kMask = true;
+};
+
+// the gcn-mode layer (gnn_sage_scatter_agg_f32 / _maxpool_f32): no centre slots, dbuf is [M, F]
+struct SbAggArgs : SbArgs {
+  static constexpr bool kCentre = false;
+};
+struct SbAggMaskArgs : SbMaskArgs {
+  static constexpr bool kCentre = false;
 };
 
 // The masked sum of sb_sum below: a centre slot adds its row, a neighbour slot (m, j) the
 // elements of dbuf[m, F:2F] whose arg byte is j. Each lane loads the 4 bytes of
 // arg[m, 4 sub : 4 sub + 4] beside its 16-B gradient load; the mask SELECTS (x or 0.f), it
 // never multiplies.
-__device__ __forceinline__ f4 sb_sum(const SbMaskArgs& a, int64_t b, int64_t e, int64_t step,
-                                     int F, int sub) {
+template <bool CENTRE>
+__device__ __forceinline__ f4 sb_sum_mask(const SbMaskArgs& a, int64_t b, int64_t e, int64_t step,
+                                          int F, int sub) {
   f4 acc = vzero<4>();
   const uint32_t m32 = static_cast<uint32_t>(a.M), k32 = static_cast<uint32_t>(a.k);
   constexpr uint32_t kAll = 0x100;  // no byte equals it: a centre slot keeps every element
@@ -149,12 +175,13 @@ __device__ __forceinline__ f4 sb_sum(const SbMaskArgs& a, int64_t b, int64_t e, 
         const uint32_t s = static_cast<uint32_t>(a.slot[q]);
         if (s < static_cast<uint32_t>(a.n_slots)) {
           const float* row;
-          if (s < m32) {
+          if (CENTRE && s < m32) {
             row = a.dbuf + static_cast<int64_t>(s) * a.ldd;
           } else {
-            const uint32_t m = (s - m32) / k32;
-            row = a.dbuf + static_cast<int64_t>(m) * a.ldd + F;
-            col[u] = (s - m32) - m * k32;
+            const uint32_t en = CENTRE ? s - m32 : s;
+            const uint32_t m = en / k32;
+            row = a.dbuf + static_cast<int64_t>(m) * a.ldd + (CENTRE ? F : 0);
+            col[u] = en - m * k32;
             win[u] = *reinterpret_cast<const uint32_t*>(a.arg + static_cast<int64_t>(m) * a.lda +
                                                         4 * sub);
           }
@@ -177,8 +204,9 @@ __device__ __forceinline__ f4 sb_sum(const SbMaskArgs& a, int64_t b, int64_t e, 
 // The sum over the slots at positions b, b + step, ... < e of the sorted list, in that order,
 // by one lane group: lane `sub` holds floats [4 sub, 4 sub + 4) of the row; kSbU loads in flight.
 // A slot outside [0, n_slots) (no builder writes one) contributes nothing.
-__device__ __forceinline__ f4 sb_sum(const SbArgs& a, int64_t b, int64_t e, int64_t step, int F,
-                                     int sub) {
+template <bool CENTRE>
+__device__ __forceinline__ f4 sb_sum_mean(const SbArgs& a, int64_t b, int64_t e, int64_t step,
+                                          int F, int sub) {
   f4 acc = vzero<4>();
   const uint32_t m32 = static_cast<uint32_t>(a.M), k32 = static_cast<uint32_t>(a.k);
   for (int64_t p = b; p < e; p += step * kSbU) {
@@ -193,10 +221,11 @@ __device__ __forceinline__ f4 sb_sum(const SbArgs& a, int64_t b, int64_t e, int6
         const uint32_t s = static_cast<uint32_t>(a.slot[q]);
         if (s < static_cast<uint32_t>(a.n_slots)) {
           const float* row;
-          if (s < m32) {
+          if (CENTRE && s < m32) {
             row = a.dbuf + static_cast<int64_t>(s) * a.ldd;
           } else {
-            row = a.dbuf + static_cast<int64_t>((s - m32) / k32) * a.ldd + F;
+            row = a.dbuf + static_cast<int64_t>((CENTRE ? s - m32 : s) / k32) * a.ldd +
+                  (CENTRE ? F : 0);
             sc[u] = a.inv_k;
           }
           v[u] = vload<4>(row + 4 * sub);
@@ -207,6 +236,14 @@ __device__ __forceinline__ f4 sb_sum(const SbArgs& a, int64_t b, int64_t e, int6
     for (int u = 0; u < kSbU; ++u) acc += v[u] * sc[u];
   }
   return acc;
+}
+
+// the sum of an argument struct: its slot decoding (kCentre) and its select (kMask)
+template <typename A>
+__device__ __forceinline__ f4 sb_sum(const A& a, int64_t b, int64_t e, int64_t step, int F,
+                                     int sub) {
+  if constexpr (A::kMask) return sb_sum_mask<A::kCentre>(a, b, e, step, F, sub);
+  else return sb_sum_mean<A::kCentre>(a, b, e, step, F, sub);
 }
 
 // the slot range of target t, empty unless it lies inside the slot array
@@ -336,22 +373,16 @@ static SbLayout sb_layout(int64_t n_slots, int64_t F) {
 
 using namespace gnn;
 
-extern "C" int64_t gnn_sage_maps_transpose_workspace_bytes(int64_t M, int64_t k) {
-  if (M < 0 || k < 0) return GNN_E_ARG;
-  const int64_t n = sb_slots(M, k);
-  if (n < 0) return GNN_E_UNSUPPORTED;
+// the workspace of a transpose over n slots: keys | sorted keys | rocPRIM's temporary
+static int64_t sb_transpose_bytes(int64_t n) {
   return 2 * sb_align(n * 4) + static_cast<int64_t>(sb_sort_temp(n > 0 ? n : 1, 32)) + (1 << 20);
 }
 
-extern "C" int gnn_sage_maps_transpose(const int64_t* cidx, const int64_t* idx, int64_t ldi,
-                                       int64_t M, int64_t k, int64_t n_prev, int64_t* ptr,
-                                       int32_t* slot, int32_t* err_flag, void* workspace,
-                                       int64_t workspace_bytes, void* stream) {
-  if (M < 0 || k < 0 || n_prev < 0 || !ptr || !err_flag || !workspace) return GNN_E_ARG;
-  if (M > 0 && (!cidx || !slot || (k > 0 && (!idx || ldi < k)))) return GNN_E_ARG;
-  const int64_t n = sb_slots(M, k);
-  if (n < 0 || n_prev >= 0x7fffffffLL) return GNN_E_UNSUPPORTED;
-  if (workspace_bytes < gnn_sage_maps_transpose_workspace_bytes(M, k)) return GNN_E_ARG;
+// the body of both transposes: the arguments are checked, n = the number of slots
+template <bool CENTRE>
+static int sb_transpose(const int64_t* cidx, const int64_t* idx, int64_t ldi, int64_t M, int64_t k,
+                        int64_t n_prev, int64_t n, int64_t* ptr, int32_t* slot, int32_t* err_flag,
+                        void* workspace, int64_t workspace_bytes, void* stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
   char* w = static_cast<char*>(workspace);
   uint32_t* k0 = reinterpret_cast<uint32_t*>(w);
@@ -363,8 +394,8 @@ extern "C" int gnn_sage_maps_transpose(const int64_t* cidx, const int64_t* idx, 
     if (static_cast<int64_t>(tb) > workspace_bytes - 2 * sb_align(n * 4)) return GNN_E_ARG;
     int64_t g = (n + kSbBlock - 1) / kSbBlock;
     g = g < 4 * kSbGrid ? g : 4 * kSbGrid;
-    hipLaunchKernelGGL(sage_slot_keys_kernel, dim3(static_cast<unsigned>(g)), dim3(kSbBlock), 0, s,
-                       cidx, idx, ldi, M, k, n_prev, k0, err_flag);
+    hipLaunchKernelGGL(sage_slot_keys_kernel<CENTRE>, dim3(static_cast<unsigned>(g)),
+                       dim3(kSbBlock), 0, s, cidx, idx, ldi, M, k, n_prev, k0, err_flag);
     hipError_t e = rocprim::radix_sort_pairs(temp, tb, k0, k1, rocprim::counting_iterator<int32_t>(0),
                                              slot, static_cast<size_t>(n), 0, bits, s);
     if (e != hipSuccess) return static_cast<int>(e);
@@ -373,6 +404,47 @@ extern "C" int gnn_sage_maps_transpose(const int64_t* cidx, const int64_t* idx, 
   hipLaunchKernelGGL(sage_slot_ptr_kernel, dim3(static_cast<unsigned>(pb)), dim3(kSbBlock), 0, s, k1,
                      n, n_prev, ptr);
   return launch_status();
+}
+
+extern "C" int64_t gnn_sage_maps_transpose_workspace_bytes(int64_t M, int64_t k) {
+  if (M < 0 || k < 0) return GNN_E_ARG;
+  const int64_t n = sb_slots(M, k);
+  if (n < 0) return GNN_E_UNSUPPORTED;
+  return sb_transpose_bytes(n);
+}
+
+extern "C" int gnn_sage_maps_transpose(const int64_t* cidx, const int64_t* idx, int64_t ldi,
+                                       int64_t M, int64_t k, int64_t n_prev, int64_t* ptr,
+                                       int32_t* slot, int32_t* err_flag, void* workspace,
+                                       int64_t workspace_bytes, void* stream) {
+  if (M < 0 || k < 0 || n_prev < 0 || !ptr || !err_flag || !workspace) return GNN_E_ARG;
+  if (M > 0 && (!cidx || !slot || (k > 0 && (!idx || ldi < k)))) return GNN_E_ARG;
+  const int64_t n = sb_slots(M, k);
+  if (n < 0 || n_prev >= 0x7fffffffLL) return GNN_E_UNSUPPORTED;
+  if (workspace_bytes < gnn_sage_maps_transpose_workspace_bytes(M, k)) return GNN_E_ARG;
+  return sb_transpose<true>(cidx, idx, ldi, M, k, n_prev, n, ptr, slot, err_flag, workspace,
+                            workspace_bytes, stream);
+}
+
+// the neighbour map alone (the gcn-mode layer): M k slots, slot e = entry (e / k, e % k)
+extern "C" int64_t gnn_sage_maps_transpose_nbr_workspace_bytes(int64_t M, int64_t k) {
+  if (M < 0 || k < 0) return GNN_E_ARG;
+  const int64_t n = sb_slots_nbr(M, k);
+  if (n < 0) return GNN_E_UNSUPPORTED;
+  return sb_transpose_bytes(n);
+}
+
+extern "C" int gnn_sage_maps_transpose_nbr(const int64_t* idx, int64_t ldi, int64_t M, int64_t k,
+                                           int64_t n_prev, int64_t* ptr, int32_t* slot,
+                                           int32_t* err_flag, void* workspace,
+                                           int64_t workspace_bytes, void* stream) {
+  if (M < 0 || k < 0 || n_prev < 0 || !ptr || !err_flag || !workspace) return GNN_E_ARG;
+  if (M > 0 && k > 0 && (!idx || !slot || ldi < k)) return GNN_E_ARG;
+  const int64_t n = sb_slots_nbr(M, k);
+  if (n < 0 || n_prev >= 0x7fffffffLL) return GNN_E_UNSUPPORTED;
+  if (workspace_bytes < gnn_sage_maps_transpose_nbr_workspace_bytes(M, k)) return GNN_E_ARG;
+  return sb_transpose<false>(nullptr, idx, ldi, M, k, n_prev, n, ptr, slot, err_flag, workspace,
+                             workspace_bytes, stream);
 }
 
 extern "C" int gnn_sage_scatter_concat_supported(int64_t feat) {
@@ -458,5 +530,74 @@ extern "C" int gnn_sage_scatter_concat_f32(const float* dbuf, int64_t ldd, const
            ldx, reinterpret_cast<int32_t*>(w), reinterpret_cast<int2*>(w + l.off_longs),
            reinterpret_cast<int2*>(w + l.off_tasks), reinterpret_cast<float*>(w + l.off_part),
            static_cast<int32_t>(l.max_long), static_cast<int32_t>(l.max_tasks)};
+  return dispatch_sage_scatter(a, feat, static_cast<hipStream_t>(stream));
+}
+
+// ---- the gcn-mode layer: dbuf is [M, F] (no centre half), the maps gnn_sage_maps_transpose_nbr's
+extern "C" int64_t gnn_sage_scatter_agg_workspace_bytes(int64_t M, int64_t k, int64_t feat) {
+  if (M < 0 || k < 0 || feat < 0) return GNN_E_ARG;
+  const int64_t n = sb_slots_nbr(M, k);
+  if (n < 0 || !gnn_sage_scatter_concat_supported(feat)) return GNN_E_UNSUPPORTED;
+  return sb_layout(n, feat).bytes;
+}
+
+extern "C" int64_t gnn_sage_scatter_agg_maxpool_workspace_bytes(int64_t M, int64_t k,
+                                                                int64_t feat) {
+  if (M < 0 || k < 0 || feat < 0) return GNN_E_ARG;
+  if (k < 1 || k > 255) return GNN_E_UNSUPPORTED;
+  return gnn_sage_scatter_agg_workspace_bytes(M, k, feat);  // the MEAN scatter's layout
+}
+
+extern "C" int gnn_sage_scatter_agg_f32(const float* dbuf, int64_t ldd, const int64_t* ptr,
+                                        const int32_t* slot, int64_t M, int64_t k, int64_t feat,
+                                        int64_t n_prev, float* dx, int64_t ldx, void* workspace,
+                                        int64_t workspace_bytes, void* stream) {
+  if (M < 0 || k < 0 || feat < 0 || n_prev < 0) return GNN_E_ARG;
+  if (!ptr || !workspace || (n_prev > 0 && !dx) || (M > 0 && (!dbuf || !slot))) return GNN_E_ARG;
+  const int64_t n = sb_slots_nbr(M, k);
+  if (n < 0 || n_prev >= 0x7fffffffLL || !gnn_sage_scatter_concat_supported(feat))
+    return GNN_E_UNSUPPORTED;
+  if (ldd < feat || ldx < feat) return GNN_E_ARG;
+  const SbLayout l = sb_layout(n, feat);
+  if (workspace_bytes < l.bytes) return GNN_E_ARG;
+  if (ldd % 4 || ldx % 4 || !aligned_to(dbuf, 16) || !aligned_to(dx, 16) ||
+      !aligned_to(workspace, 16))
+    return GNN_E_ALIGN;
+  if (n_prev == 0) return GNN_OK;
+  char* w = static_cast<char*>(workspace);
+  SbAggArgs a{{dbuf, ldd, ptr, slot, M, k, n_prev, n, k > 0 ? 1.0f / static_cast<float>(k) : 0.f,
+               dx, ldx, reinterpret_cast<int32_t*>(w), reinterpret_cast<int2*>(w + l.off_longs),
+               reinterpret_cast<int2*>(w + l.off_tasks), reinterpret_cast<float*>(w + l.off_part),
+               static_cast<int32_t>(l.max_long), static_cast<int32_t>(l.max_tasks)}};
+  return dispatch_sage_scatter(a, feat, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int gnn_sage_scatter_agg_maxpool_f32(const float* dbuf, int64_t ldd, const uint8_t* arg,
+                                                int64_t lda, const int64_t* ptr,
+                                                const int32_t* slot, int64_t M, int64_t k,
+                                                int64_t feat, int64_t n_prev, float* dx,
+                                                int64_t ldx, void* workspace,
+                                                int64_t workspace_bytes, void* stream) {
+  if (M < 0 || k < 0 || feat < 0 || n_prev < 0) return GNN_E_ARG;
+  if (!ptr || !workspace || (n_prev > 0 && !dx) || (M > 0 && (!dbuf || !slot || !arg)))
+    return GNN_E_ARG;
+  const int64_t n = sb_slots_nbr(M, k);
+  if (n < 0 || n_prev >= 0x7fffffffLL || !gnn_sage_scatter_concat_supported(feat) || k < 1 ||
+      k > 255)
+    return GNN_E_UNSUPPORTED;
+  if (ldd < feat || ldx < feat || lda < feat) return GNN_E_ARG;
+  const SbLayout l = sb_layout(n, feat);
+  if (workspace_bytes < l.bytes) return GNN_E_ARG;
+  if (ldd % 4 || ldx % 4 || lda % 4 || !aligned_to(dbuf, 16) || !aligned_to(dx, 16) ||
+      !aligned_to(arg, 4) || !aligned_to(workspace, 16))
+    return GNN_E_ALIGN;
+  if (n_prev == 0) return GNN_OK;
+  char* w = static_cast<char*>(workspace);
+  SbAggMaskArgs a{{{dbuf, ldd, ptr, slot, M, k, n_prev, n, 1.f, dx, ldx,
+                    reinterpret_cast<int32_t*>(w), reinterpret_cast<int2*>(w + l.off_longs),
+                    reinterpret_cast<int2*>(w + l.off_tasks),
+                    reinterpret_cast<float*>(w + l.off_part), static_cast<int32_t>(l.max_long),
+                    static_cast<int32_t>(l.max_tasks)},
+                   arg, lda}};
   return dispatch_sage_scatter(a, feat, static_cast<hipStream_t>(stream));
 }

@@ -45,7 +45,8 @@ template <> struct SageElem<bf16_t> { static constexpr int kVec = 8, kU = GNN_SA
 
 // kArgmaxF: the argmax index stored as fp32 (exact below 2^24) -- what the SageLayer's
 // torch.cat([self_feats, argmax]) promotes it to (GraphSAGE/GraphSAGE.py:17, graph_utils.py:8)
-// kMaxPoolArg (the training layer, GATHER + SELF form only; not a public mode number): the value
+// kMaxPoolArg (the training layers, GATHER form only, with the centre half or -- gcn mode --
+// without it; not a public mode number): the value
 // max-pool AND its winner -- the fp32 value at the slot that wins under `beats` into out, that
 // slot as a uint8 into arg_out (k <= 255). The slot is kArgmax's; the value is kMaxPool's up to
 // the sign of a zero and the payload of a NaN (nanmax keeps the LAST of equal values and any
@@ -86,8 +87,8 @@ __global__ __launch_bounds__(kSageBlock) void sage_aggregate_kernel(
     const int64_t* __restrict__ self_idx = nullptr, float* __restrict__ self_out = nullptr,
     int64_t ld_self = 0, const int64_t* __restrict__ live = nullptr,
     uint8_t* __restrict__ arg_out = nullptr, int64_t lda = 0) {
-  static_assert(MODE != kMaxPoolArg || (GATHER && SELF && NCH == 1 && VW % 4 == 0),
-                "the winner-recording mode exists in the GATHER + SELF vector form only");
+  static_assert(MODE != kMaxPoolArg || (GATHER && NCH == 1 && VW % 4 == 0),
+                "the winner-recording mode exists in the GATHER vector form only");
   typedef Row<T, VW> RX;
   constexpr int EPI = kWave / LPR;
   const int lane = threadIdx.x & (kWave - 1);
@@ -331,18 +332,35 @@ static int run_sage(SageArgsT<T> a, int32_t mode, bool vec) {
   return GNN_OK;
 }
 
-// kMaxPoolArg: feat a power of two, one column chunk per lane (feat / kVec <= 64 lanes)
-template <int LPR, typename T>
+// kMaxPoolArg: feat a power of two, one column chunk per lane (feat / kVec <= 64 lanes).
+// SELF: the concat layer's form; off: the aggregate alone (the gcn-mode layer)
+template <int LPR, bool SELF, typename T>
 static int launch_sage_arg(const SageArgsT<T>& a) {
   constexpr int VW = SageElem<T>::kVec;
   const int64_t blocks = (a.M + kSageWaves - 1) / kSageWaves;
   if (blocks > 0x7fffffffLL) return GNN_E_UNSUPPORTED;
   hipLaunchKernelGGL(
-      (sage_aggregate_kernel<T, VW, LPR, 1, kMaxPoolArg, true, SageElem<T>::kU, true>),
+      (sage_aggregate_kernel<T, VW, LPR, 1, kMaxPoolArg, true, SageElem<T>::kU, SELF>),
       dim3(static_cast<unsigned>(blocks)), dim3(kSageBlock), GNN_SAGE_LDS_PAD, a.s, a.src, a.ld_row,
       a.ld_m, a.n_table, a.idx, a.ldi, a.M, a.k, a.feat, a.out, a.ldo, a.err, a.self_idx,
       a.self_out, a.ld_self, nullptr, a.arg, a.lda);
   return launch_status();
+}
+
+template <bool SELF, typename T>
+static int dispatch_sage_arg(const SageArgsT<T>& a) {
+  constexpr int VX = SageElem<T>::kVec;
+  switch (a.feat / VX) {
+    case 1: return launch_sage_arg<1, SELF>(a);
+    case 2: return launch_sage_arg<2, SELF>(a);
+    case 4: return launch_sage_arg<4, SELF>(a);
+    case 8: return launch_sage_arg<8, SELF>(a);
+    case 16: return launch_sage_arg<16, SELF>(a);
+    case 32: return launch_sage_arg<32, SELF>(a);
+    default:
+      if constexpr (VX == 4) return launch_sage_arg<64, SELF>(a);  // feat = 256 in fp32
+      return GNN_E_UNSUPPORTED;
+  }
 }
 
 // The vector path of T needs whole lanes per row (feat and every pitch of T a multiple of
@@ -373,7 +391,8 @@ template <typename T>
 static int sage_gather_aggregate_entry(const T* table, int64_t ldt, int64_t n_table,
                                        const int64_t* idx, int64_t ldi, int64_t M, int64_t k,
                                        int64_t feat, int32_t mode, void* out, int64_t ldo,
-                                       int32_t* err_flag, void* stream) {
+                                       int32_t* err_flag, void* stream,
+                                       const int64_t* live = nullptr) {
   if (M < 0 || k < 0 || feat < 0 || n_table < 0 || (mode < kMean || mode > kMaxPool))
     return GNN_E_ARG;  // GNN_SAGE_ARGMAX_F32: the concat entries only
   if (M == 0 || feat == 0) return GNN_OK;
@@ -382,8 +401,21 @@ static int sage_gather_aggregate_entry(const T* table, int64_t ldt, int64_t n_ta
   const bool vec = sage_src_vec(table, feat, ldt, 0) && ldo % 4 == 0 &&
                    aligned_to(out, mode != kArgmax ? 16 : 32);
   SageArgsT<T> a{table, ldt, 0, n_table, idx, ldi, M, k, feat, out, ldo, err_flag,
-                 static_cast<hipStream_t>(stream)};
+                 static_cast<hipStream_t>(stream), nullptr, nullptr, 0, live};
   return run_sage<true>(a, mode, vec);
+}
+
+// gnn_sage_gather_aggregate_live_{f32,bf16}: MEAN / MAXPOOL (the gcn-mode inference layer's
+// aggregates) over rows [0, min(*live, M)) of a buffer of capacity M; live == nullptr: all M
+template <typename T>
+static int sage_gather_aggregate_live_entry(const T* table, int64_t ldt, int64_t n_table,
+                                            const int64_t* idx, int64_t ldi, int64_t M,
+                                            const int64_t* live, int64_t k, int64_t feat,
+                                            int32_t mode, float* out, int64_t ldo,
+                                            int32_t* err_flag, void* stream) {
+  if (mode != kMean && mode != kMaxPool) return GNN_E_ARG;
+  return sage_gather_aggregate_entry<T>(table, ldt, n_table, idx, ldi, M, k, feat, mode, out, ldo,
+                                        err_flag, stream, live);
 }
 
 template <typename T>
@@ -433,17 +465,29 @@ static int sage_gather_concat_arg_entry(const T* table, int64_t ldt, int64_t n_t
   if (M == 0) return GNN_OK;
   SageArgsT<T> a{table, ldt, 0, n_table, idx, ldi, M, k, feat, out, ldo, err_flag,
                  static_cast<hipStream_t>(stream), self_idx, self_out, ld_self, nullptr, arg, lda};
-  switch (feat / VX) {
-    case 1: return launch_sage_arg<1>(a);
-    case 2: return launch_sage_arg<2>(a);
-    case 4: return launch_sage_arg<4>(a);
-    case 8: return launch_sage_arg<8>(a);
-    case 16: return launch_sage_arg<16>(a);
-    case 32: return launch_sage_arg<32>(a);
-    default:
-      if constexpr (VX == 4) return launch_sage_arg<64>(a);  // feat = 256 in fp32
-      return GNN_E_UNSUPPORTED;
-  }
+  return dispatch_sage_arg<true>(a);
+}
+
+// gnn_sage_gather_aggregate_arg_{f32,bf16}: the same without the centre half (the gcn-mode
+// SageLayer feeds the aggregate alone into its Linear): out[m, f] = max_j table[idx[m, j], f]
+// and its winner, the rules and the shapes of the concat entry above.
+template <typename T>
+static int sage_gather_aggregate_arg_entry(const T* table, int64_t ldt, int64_t n_table,
+                                           const int64_t* idx, int64_t ldi, int64_t M, int64_t k,
+                                           int64_t feat, float* out, int64_t ldo, uint8_t* arg,
+                                           int64_t lda, int32_t* err_flag, void* stream) {
+  constexpr int VX = SageElem<T>::kVec;
+  if (M < 0 || k < 0 || feat < 0 || n_table < 0) return GNN_E_ARG;
+  if (!table || !idx || !out || !arg || !err_flag) return GNN_E_ARG;
+  if (!sage_concat_arg_shape(feat, k) || feat % VX != 0) return GNN_E_UNSUPPORTED;
+  if (ldt < feat || ldo < feat || lda < feat || ldi < k) return GNN_E_ARG;
+  if (ldt % VX || ldo % 4 || lda % 4 || !aligned_to(table, 16) || !aligned_to(out, 16) ||
+      !aligned_to(arg, 4))
+    return GNN_E_ALIGN;
+  if (M == 0) return GNN_OK;
+  SageArgsT<T> a{table, ldt, 0, n_table, idx, ldi, M, k, feat, out, ldo, err_flag,
+                 static_cast<hipStream_t>(stream), nullptr, nullptr, 0, nullptr, arg, lda};
+  return dispatch_sage_arg<false>(a);
 }
 
 }  // namespace gnn

@@ -19,7 +19,11 @@ Hot path on gfx950:
   the weight gradient in one masked pass and the concat gather's adjoint on the device
   (``csrc/sage_bwd.hip``) backward; per MAXPOOL layer ``_SageMaxPoolTrainLayerFn``: the concat
   gather records the winning neighbour as one byte per (row, feature), the adjoint sums the
-  gradient through that mask in a fixed order (no ``index_put_``, no float atomics).
+  gradient through that mask in a fixed order (no ``index_put_``, no float atomics);
+* ``gcn=True`` (``relu(W . agg)``, the sampler's maps holding each node among its neighbours):
+  the same over the aggregate alone -- inference as one gather-aggregate into an [M, F] buffer
+  plus the MFMA GEMM (a pending batch stays pending), training as ``_SageGcnTrainLayerFn``
+  with the adjoint of the gcn gather on the device (``SAGE_GCN_FUSED``).
 """
 from __future__ import annotations
 
@@ -32,9 +36,11 @@ from torch import nn
 from .graph import from_coo
 from .ops import (_bf16_inference_only, _masked_grad, _transform_or_mm, gather_rows,
                   gcn_transform, gemm_tn_masked, linear_relu_classify, sage_aggregate,
-                  sage_gather_aggregate, sage_gather_concat, sage_gather_concat_arg, sage_layer,
-                  sage_maps_transpose, sage_scatter_concat, sage_scatter_concat_maxpool,
-                  sage_train_layer_supported, spmm_forward)
+                  sage_gather_aggregate, sage_gather_aggregate_arg, sage_gather_concat,
+                  sage_gather_concat_arg, sage_layer, sage_maps_transpose,
+                  sage_maps_transpose_nbr, sage_scatter_agg, sage_scatter_agg_maxpool,
+                  sage_scatter_concat, sage_scatter_concat_maxpool, sage_train_layer_supported,
+                  spmm_forward)
 
 # the inference SageLayer GEMM relu([self | agg] @ W^T) runs on the hand-written MFMA kernel
 # (gnn_linear_relu_f32). With the split-bf16 arithmetic (the default, ops.set_transform_precision)
@@ -326,6 +332,13 @@ def _fused_sage_layer(block, center, neigh: Gathered, dense: nn.Linear | None = 
             buf[:, :n].copy_(center)  # (widens a bfloat16 centre tensor)
         sage_gather_aggregate(neigh.table, neigh.index, "MEAN", check=not neigh.trusted,
                               out=buf[:, n:])
+    return _sage_layer_gemm(block, buf, dense)
+
+
+def _sage_layer_gemm(block, buf, dense):
+    """relu(buf @ W^T) of an inference SageLayer over its input buffer ([self | agg], or the
+    aggregate alone in gcn mode); ``(y, logits)`` where ``dense`` ran in the epilogue."""
+    M = buf.shape[0]
     W = block.weight.weight
     if dense is not None and _sage_gemm_on_mfma(M):
         yl = linear_relu_classify(buf, W, dense.weight, dense.bias)
@@ -344,6 +357,37 @@ def _fused_sage_layer(block, center, neigh: Gathered, dense: nn.Linear | None = 
         zero = torch.zeros(W.shape[0], dtype=W.dtype, device=W.device)
         block.__dict__["_zero_bias"] = zero
     return torch._addmm_activation(zero, buf, W.t())
+
+
+# The gcn-mode layers (GraphSAGE(.., gcn=True): relu(W . agg), no centre half) on their own
+# kernels: inference through ``_fused_gcn_layer``, training through ``_SageGcnTrainLayerFn``.
+# False: the paths from before -- the centre gather nobody reads, ``_GatherMeanAgg`` /
+# ``_GatherMaxPoolAgg``, torch's linear and relu (tools/sage_train_ab.py --gcn flips it).
+SAGE_GCN_FUSED = True
+
+
+def _fused_gcn_layer(block, neigh: Gathered, dense: nn.Linear | None = None, agg: str = 'MEAN'):
+    """Inference SageLayer in gcn mode on a (table, index map) aggregate: ONE gather-aggregate
+    ('MEAN' / 'MAXPOOL', the table fp32 or bf16) straight into an [M, F] buffer, then
+    ``_sage_layer_gemm`` (GraphSAGE.py:13-14, 18-20 over the gathers of :48-49; no centre gather:
+    the layer never reads it). ``neigh.live`` (a pending batch): the live gather and the live
+    GEMM run on the buffers' capacity under the concat layer's conditions, else one host read."""
+    live = neigh.live
+    W = block.weight.weight
+    if live is not None and (dense is not None or not _sage_gemm_on_mfma(neigh.index.shape[0])
+                             or W.dtype != torch.float32):
+        neigh, live = _trim(neigh), None
+    M = neigh.index.shape[0]
+    buf = torch.empty((M, block.input_size), dtype=torch.float32, device=neigh.table.device)
+    sage_gather_aggregate(neigh.table, neigh.index, agg, check=not neigh.trusted, out=buf,
+                          live=live)
+    if live is not None:
+        y = gcn_transform(buf, W, relu=True, live=live)
+        if y is not None:
+            return y
+        # the transform does not take the shape: the rows past the count are never read
+        buf = buf[:int(live.item())]
+    return _sage_layer_gemm(block, buf, dense)
 
 
 # The training SageLayer over a sampler batch as ONE autograd function (``_SageTrainLayerFn``).
@@ -466,6 +510,82 @@ class _SageMaxPoolTrainLayerFn(torch.autograd.Function):
         return d_table, dW, None, None
 
 
+def _gcn_maxpool_scatter_torch(dbuf, arg, idx, n_prev):
+    """The masked sum of ``sage_scatter_agg_maxpool`` in torch, for a shape it declines: each
+    (row, feature) onto the table row of its winner by index_put_ (float atomics)."""
+    out = torch.zeros((n_prev, dbuf.shape[1]), dtype=dbuf.dtype, device=dbuf.device)
+    rows = idx.gather(1, arg.to(torch.int64))                     # [M, F] table rows
+    cols = torch.arange(dbuf.shape[1], device=dbuf.device).expand_as(rows)
+    return out.index_put_((rows, cols), dbuf, accumulate=True)
+
+
+class _SageGcnTrainLayerFn(torch.autograd.Function):
+    """relu(W . agg_j table[idx[:, j]]) (the gcn-mode SageLayer, GraphSAGE/GraphSAGE.py:13-14,
+    18-20 over the gathers of :48-49; ``agg`` 'MEAN' or 'MAXPOOL') with autograd w.r.t. W and,
+    where it asks for it, the fp32 table.
+
+    Forward: ``sage_gather_aggregate`` (MEAN) or ``sage_gather_aggregate_arg`` (MAXPOOL: the
+    winner of every (row, feature) as one byte) writes buf [M, F], ``gcn_transform`` gives
+    y = relu(buf W^T). Backward as ``_SageTrainLayerFn``: dW = dY'^T buf in one masked pass; only
+    for a table that requires grad dBuf = dY' W and dX = ``sage_scatter_agg`` /
+    ``sage_scatter_agg_maxpool`` over ``sage_maps_transpose_nbr``: M k slots, fp32 sums in slot
+    order, no float atomics. The maps are the device sampler's: nothing checked or read back."""
+
+    @staticmethod
+    def forward(ctx, table, W, idx, agg):
+        arg = None
+        if agg == 'MAXPOOL':
+            r = sage_gather_aggregate_arg(table, idx, check=False)
+            if r is None:  # sage_train_layer_supported said the gather takes the shape
+                raise RuntimeError("the max-pool gather refused a shape it reports as covered")
+            buf, arg = r
+        else:
+            buf = sage_gather_aggregate(table, idx, "MEAN", check=False)
+        y = gcn_transform(buf, W, relu=True)
+        if y is None:
+            raise RuntimeError("the SageLayer transform refused a shape it reports as covered")
+        ctx.save_for_backward(buf, y, W, idx, arg)
+        ctx.n_prev = table.shape[0]
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        buf, y, W, idx, arg = ctx.saved_tensors
+        d_table = dW = g = None
+        if ctx.needs_input_grad[1]:
+            r = gemm_tn_masked(buf, dy, y, 1.0, False, trans=True)
+            if r is not None:
+                dW = r[0]
+            else:
+                g = _masked_grad(dy, y, 1.0)
+                dW = torch.mm(g.t(), buf)
+        if ctx.needs_input_grad[0]:
+            if g is None:
+                g = _masked_grad(dy, y, 1.0)
+            dbuf = _transform_or_mm(g, W.t().contiguous())
+            tr = sage_maps_transpose_nbr(idx, ctx.n_prev, check=False)
+            if tr is not None:
+                d_table = (sage_scatter_agg(dbuf, tr, ctx.n_prev) if arg is None else
+                           sage_scatter_agg_maxpool(dbuf, arg, tr, ctx.n_prev))
+            if d_table is None:  # a shape the kernel declines
+                d_table = (_scatter_rows(dbuf, idx, ctx.n_prev, 1.0 / idx.shape[1])
+                           if arg is None else
+                           _gcn_maxpool_scatter_torch(dbuf, arg, idx, ctx.n_prev))
+        return d_table, dW, None, None
+
+
+def _sage_gcn_train_layer(block, neigh: Gathered, agg: str):
+    """The gcn-mode training SageLayer on a trusted map, or None where ``_SageGcnTrainLayerFn``
+    does not cover the layer (the caller takes the unfused path)."""
+    table, W, idx = neigh.table, block.weight.weight, neigh.index
+    if (idx.dim() != 2 or idx.dtype != torch.int64 or idx.shape[0] == 0
+            or not (W.requires_grad or table.requires_grad)
+            or (table.dtype == torch.bfloat16 and table.requires_grad)  # raises as before
+            or not sage_train_layer_supported(table, W, idx.shape[1], agg, gcn=True)):
+        return None
+    return _SageGcnTrainLayerFn.apply(table, W, idx, agg)
+
+
 def _sage_train_layer(block, center: Gathered, neigh: Gathered, agg: str = 'MEAN'):
     """The training SageLayer on trusted maps over one table, or None where
     ``_SageTrainLayerFn`` / ``_SageMaxPoolTrainLayerFn`` does not cover the layer (the caller
@@ -500,8 +620,11 @@ class GraphSAGE(nn.Module):
             self.dense = nn.Linear(out_size, class_size)
 
     def _fused_ok(self, block, center, neigh) -> bool:
-        if torch.is_grad_enabled() or block.gcn or not isinstance(neigh, Gathered):
+        if torch.is_grad_enabled() or not isinstance(neigh, Gathered):
             return False
+        if block.gcn:  # the aggregate alone (``_fused_gcn_layer``): no centre rows to place
+            return (SAGE_GCN_FUSED and self.agg_func in ('MEAN', 'MAXPOOL')
+                    and neigh.table.dtype in (torch.float32, torch.bfloat16))
         if self.agg_func == 'MEAN':
             return True
         # MAX / MAXPOOL: the one-launch concat form (centre and neighbours from one table)
@@ -520,6 +643,13 @@ class GraphSAGE(nn.Module):
                 and isinstance(neigh, Gathered) and center.table is neigh.table
                 and center.trusted and neigh.trusted)
 
+    def _train_gcn_fused_ok(self, block, neigh) -> bool:
+        """The gcn-mode training layer (``_SageGcnTrainLayerFn``): MEAN or MAXPOOL over the
+        aggregate alone, the neighbours Gathered through the device sampler's (trusted) map."""
+        return (SAGE_GCN_FUSED and torch.is_grad_enabled() and block.gcn
+                and self.agg_func in ('MEAN', 'MAXPOOL')
+                and isinstance(neigh, Gathered) and neigh.trusted)
+
     def forward(self, center_feats_data, center_nodes_map, center_neigh_feats_data, center_neigh_nodes_map,
                 contexts_negatives_feats_data, contexts_negatives_nodes_map, contexts_negatives_neigh_feats_data,
                 contexts_negatives_neigh_nodes_map, contexts_negatives_shape):
@@ -530,8 +660,12 @@ class GraphSAGE(nn.Module):
             for i, block in enumerate(self.sage_blocks):
                 if self._fused_ok(block, center, neigh):
                     last = i == self.num_layers - 1 and not self.Unsupervised
-                    feats_data = _fused_sage_layer(block, center, neigh,
-                                                   self.dense if last else None, self.agg_func)
+                    dense = self.dense if last else None
+                    if block.gcn:
+                        feats_data = _fused_gcn_layer(block, neigh, dense, self.agg_func)
+                    else:
+                        feats_data = _fused_sage_layer(block, center, neigh, dense,
+                                                       self.agg_func)
                     if isinstance(feats_data, tuple):  # the classifier ran in the epilogue
                         feats_data, classes = feats_data
                 else:
@@ -539,6 +673,8 @@ class GraphSAGE(nn.Module):
                     feats_data = None
                     if self._train_fused_ok(block, center, neigh):
                         feats_data = _sage_train_layer(block, center, neigh, self.agg_func)
+                    elif self._train_gcn_fused_ok(block, neigh):
+                        feats_data = _sage_gcn_train_layer(block, neigh, self.agg_func)
                     if feats_data is None:
                         if isinstance(center, Gathered):
                             center = _gather(center.table, center.index, center.trusted)

@@ -1611,15 +1611,21 @@ def _sage_dst(out, M, F, mode, dev):
 
 
 def sage_gather_aggregate(table: torch.Tensor, idx: torch.Tensor, agg_func: str = "MEAN",
-                          check: bool = True, out: torch.Tensor | None = None) -> torch.Tensor:
+                          check: bool = True, out: torch.Tensor | None = None,
+                          live: torch.Tensor | None = None) -> torch.Tensor:
     """Aggregator(torch.embedding(table, idx)) fused: [M, k] int64 indices into table [n, F].
     A bfloat16 ``table`` (the stored input features; gnn_sage_gather_aggregate_bf16) is read
     at 2 bytes per element, widened exactly and reduced in fp32: the result is fp32 (int64 for
-    'MAX'), and 'MAX' / 'MAXPOOL' are exact functions of the stored values."""
+    'MAX'), and 'MAX' / 'MAXPOOL' are exact functions of the stored values.
+    ``live`` ('MEAN' / 'MAXPOOL' only): a device int64 scalar; rows [0, min(live, M)) only
+    (gnn_sage_gather_aggregate_live_f32 / _bf16, M = the capacity of a sampled batch whose
+    frontier size the host never read); the other rows of the result are left as they were."""
     if agg_func not in SAGE_KINDS:
         raise RuntimeError(f"unknown agg_func {agg_func!r}")
+    if live is not None and agg_func not in ("MEAN", "MAXPOOL"):
+        raise ValueError("live= is supported for 'MEAN' and 'MAXPOOL' only")
     _f32_or_bf16(table, "table")
-    _require_device(table, idx)
+    _require_device(table, idx, live)
     table = _rows_x(table, "table")
     _bf16_inference_only(table, "sage_gather_aggregate")
     if idx.dim() != 2:
@@ -1636,6 +1642,19 @@ def sage_gather_aggregate(table: torch.Tensor, idx: torch.Tensor, agg_func: str 
         return out.fill_(_EMPTY_FILL[mode])
     err = _err_flag(table.device, check)
     lib = _lib.load()
+    if live is not None:
+        if live.dtype != torch.int64 or live.numel() != 1:
+            raise TypeError("live must be a one-element int64 device tensor")
+        fn, name = ((lib.gnn_sage_gather_aggregate_live_bf16, "gnn_sage_gather_aggregate_live_bf16")
+                    if _bf16(table) else
+                    (lib.gnn_sage_gather_aggregate_live_f32, "gnn_sage_gather_aggregate_live_f32"))
+        _lib.check(fn(
+            table.data_ptr(), table.stride(0), table.shape[0], idx.data_ptr(), idx.stride(0), M,
+            live.data_ptr(), k, F, mode, out.data_ptr(), out.stride(0), err.data_ptr(),
+            _lib.stream_handle(table.device)), name)
+        if check:
+            _check_err(err, "sage_gather_aggregate")
+        return out
     fn, name = ((lib.gnn_sage_gather_aggregate_bf16, "gnn_sage_gather_aggregate_bf16")
                 if _bf16(table) else
                 (lib.gnn_sage_gather_aggregate_f32, "gnn_sage_gather_aggregate_f32"))
@@ -1716,6 +1735,9 @@ class SageMapsT(NamedTuple):
     slot: torch.Tensor   # int32 [M * (k + 1)]
     M: int
     k: int
+    # False: the maps of the neighbour map alone (``sage_maps_transpose_nbr``, the gcn-mode
+    # layer): M * k slots, slot e the entry (e // k, e % k), no centre slots
+    centre: bool = True
 
 
 def sage_maps_transpose(center_idx: torch.Tensor, neigh_idx: torch.Tensor, n_prev: int,
@@ -1781,7 +1803,8 @@ def sage_scatter_concat(dbuf: torch.Tensor, tr: SageMapsT, n_prev: int,
     n_prev = int(n_prev)
     M, k = tr.M, tr.k
     F = dbuf.shape[1] // 2
-    if dbuf.shape[0] != M or tr.ptr.numel() != n_prev + 1 or tr.slot.numel() != M * (k + 1):
+    if (dbuf.shape[0] != M or tr.ptr.numel() != n_prev + 1 or tr.slot.numel() != M * (k + 1)
+            or not tr.centre):
         raise ValueError("dbuf, the transposed maps and n_prev do not belong together")
     if tr.ptr.dtype != torch.int64 or tr.slot.dtype != torch.int32:
         raise TypeError("the transposed maps must be (int64 ptr, int32 slot)")
@@ -1882,7 +1905,7 @@ def sage_scatter_concat_maxpool(dbuf: torch.Tensor, arg: torch.Tensor, tr: SageM
     M, k = tr.M, tr.k
     F = dbuf.shape[1] // 2
     if (dbuf.shape[0] != M or tuple(arg.shape) != (M, F) or tr.ptr.numel() != n_prev + 1
-            or tr.slot.numel() != M * (k + 1)):
+            or tr.slot.numel() != M * (k + 1) or not tr.centre):
         raise ValueError("dbuf, arg, the transposed maps and n_prev do not belong together")
     if tr.ptr.dtype != torch.int64 or tr.slot.dtype != torch.int32:
         raise TypeError("the transposed maps must be (int64 ptr, int32 slot)")
@@ -1914,12 +1937,181 @@ def sage_scatter_concat_maxpool(dbuf: torch.Tensor, arg: torch.Tensor, tr: SageM
     return dx
 
 
+def sage_gather_aggregate_arg(table: torch.Tensor, idx: torch.Tensor, check: bool = True):
+    """``sage_gather_aggregate(table, idx, 'MAXPOOL')`` that also records the winner
+    (gnn_sage_gather_aggregate_arg_f32 / _bf16): returns ``(out, arg)`` -- out float32 [M, F] =
+    max_j table[idx[:, j]], arg uint8 [M, F] the winning neighbour column. The gcn-mode twin of
+    ``sage_gather_concat_arg`` (no centre half), with its rules: the first maximum, a NaN first
+    (``sage_gather_aggregate(table, idx, 'MAX')`` as bytes); out[m, f] is the value AT
+    arg[m, f]. None where the kernel does not take the shape (F not a power of two in [4, 256]
+    -- [8, 256] for a bfloat16 table --, k outside [1, 255], a table view whose rows are not
+    16-B lanes)."""
+    _f32_or_bf16(table, "table")
+    _require_device(table, idx)
+    table = _rows_x(table, "table")
+    _bf16_inference_only(table, "sage_gather_aggregate_arg")
+    if idx.dim() != 2:
+        raise ValueError("idx must be [M, k]")
+    idx = idx.to(torch.int64)
+    if idx.stride(1) != 1:
+        idx = idx.contiguous()
+    M, k = idx.shape
+    F = table.shape[1]
+    lib = _lib.load()
+    vec = 8 if _bf16(table) else 4
+    if (not lib.gnn_sage_gather_aggregate_arg_supported(F, k) or F % vec
+            or table.stride(0) % vec or table.data_ptr() % 16):
+        return None
+    out = torch.empty((M, F), dtype=torch.float32, device=table.device)
+    arg = torch.empty((M, F), dtype=torch.uint8, device=table.device)
+    if M == 0:
+        return out, arg
+    err = _err_flag(table.device, check)
+    fn, name = ((lib.gnn_sage_gather_aggregate_arg_bf16, "gnn_sage_gather_aggregate_arg_bf16")
+                if _bf16(table) else
+                (lib.gnn_sage_gather_aggregate_arg_f32, "gnn_sage_gather_aggregate_arg_f32"))
+    _lib.check(fn(
+        table.data_ptr(), table.stride(0), table.shape[0], idx.data_ptr(), idx.stride(0), M, k, F,
+        out.data_ptr(), F, arg.data_ptr(), F, err.data_ptr(), _lib.stream_handle(table.device)),
+        name)
+    if check:
+        _check_err(err, "sage_gather_aggregate_arg")
+    return out, arg
+
+
+def sage_maps_transpose_nbr(neigh_idx: torch.Tensor, n_prev: int,
+                            check: bool = True) -> SageMapsT | None:
+    """The transposed maps of ``sage_gather_aggregate(table, neigh_idx)`` over a table of
+    ``n_prev`` rows (gnn_sage_maps_transpose_nbr): ``sage_maps_transpose`` without the centre
+    slots -- slot e is the entry (e // k, e % k); exactly numpy's stable argsort of
+    ``neigh_idx.ravel()`` with its bincount / cumsum. The result has ``centre=False``.
+    ``check``: an index outside [0, n_prev) raises IndexError (one host read). None where M k
+    does not fit an int32 slot id."""
+    _require_device(neigh_idx)
+    if neigh_idx.dim() != 2:
+        raise ValueError("neigh_idx must be [M, k]")
+    if neigh_idx.dtype != torch.int64:
+        raise TypeError("neigh_idx must be int64")
+    n_prev = int(n_prev)
+    if n_prev < 0:
+        raise ValueError("n_prev must not be negative")
+    if ((neigh_idx.stride(1) != 1 and neigh_idx.shape[1] > 1)
+            or (neigh_idx.shape[0] > 1 and neigh_idx.stride(0) < neigh_idx.shape[1])):
+        neigh_idx = neigh_idx.contiguous()
+    M, k = neigh_idx.shape
+    dev = neigh_idx.device
+    if M == 0 or k == 0:  # no slot: every list is empty
+        return SageMapsT(torch.zeros(n_prev + 1, dtype=torch.int64, device=dev),
+                         torch.empty(0, dtype=torch.int32, device=dev), M, k, False)
+    lib = _lib.load()
+    nbytes = int(lib.gnn_sage_maps_transpose_nbr_workspace_bytes(M, k))
+    if nbytes == _lib.E_UNSUPPORTED or n_prev >= 2 ** 31 - 1:
+        return None
+    ptr = torch.empty(n_prev + 1, dtype=torch.int64, device=dev)
+    slot = torch.empty(M * k, dtype=torch.int32, device=dev)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    err = _err_flag(dev, check)
+    ldi = neigh_idx.stride(0) if M > 1 else k  # a single row's stride is never used
+    _lib.check(lib.gnn_sage_maps_transpose_nbr(
+        neigh_idx.data_ptr(), ldi, M, k, n_prev, ptr.data_ptr(), slot.data_ptr(), err.data_ptr(),
+        ws.data_ptr(), ws.numel(), _lib.stream_handle(dev)), "gnn_sage_maps_transpose_nbr")
+    if check:
+        _check_err(err, "sage_maps_transpose_nbr")
+    return SageMapsT(ptr, slot, M, k, False)
+
+
+def _scatter_agg(dbuf, arg, tr, n_prev, out):
+    """``sage_scatter_agg`` (arg None) / ``sage_scatter_agg_maxpool``."""
+    _require_device(dbuf, arg, tr.ptr, tr.slot, out)
+    if dbuf.dtype != torch.float32:
+        raise TypeError(f"dbuf must be float32 (got {dbuf.dtype})")
+    if arg is not None and arg.dtype != torch.uint8:
+        raise TypeError(f"arg must be uint8 (got {arg.dtype})")
+    if dbuf.dim() != 2:
+        raise ValueError("dbuf must be [M, F]")
+    n_prev = int(n_prev)
+    M, k = tr.M, tr.k
+    F = dbuf.shape[1]
+    if (tr.centre or dbuf.shape[0] != M or tr.ptr.numel() != n_prev + 1
+            or tr.slot.numel() != M * k or (arg is not None and tuple(arg.shape) != (M, F))):
+        raise ValueError("dbuf, arg, the transposed maps (sage_maps_transpose_nbr) and n_prev do "
+                         "not belong together")
+    if tr.ptr.dtype != torch.int64 or tr.slot.dtype != torch.int32:
+        raise TypeError("the transposed maps must be (int64 ptr, int32 slot)")
+    if out is not None and (out.shape != (n_prev, F) or out.dtype != torch.float32
+                            or not out.is_contiguous() or out.data_ptr() % 16):
+        raise ValueError(f"out must be a contiguous float32 [{n_prev}, {F}] tensor")
+    lib = _lib.load()
+    if k < 1 or (arg is not None and k > 255) or not lib.gnn_sage_scatter_concat_supported(F):
+        return None
+    if M == 0:
+        return (torch.zeros((n_prev, F), dtype=torch.float32, device=dbuf.device)
+                if out is None else out.zero_())
+    if (dbuf.stride(1) != 1 or (M > 1 and (dbuf.stride(0) % 4 or dbuf.stride(0) < F))
+            or dbuf.data_ptr() % 16):
+        return None
+    if arg is not None and (arg.stride(1) != 1 or arg.data_ptr() % 4
+                            or (M > 1 and (arg.stride(0) % 4 or arg.stride(0) < F))):
+        return None
+    query = (lib.gnn_sage_scatter_agg_workspace_bytes if arg is None else
+             lib.gnn_sage_scatter_agg_maxpool_workspace_bytes)
+    nbytes = int(query(M, k, F))
+    if nbytes < 0:
+        return None
+    dx = out if out is not None else torch.empty((n_prev, F), dtype=torch.float32,
+                                                 device=dbuf.device)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dbuf.device)
+    ptr, slot = tr.ptr.contiguous(), tr.slot.contiguous()
+    ldd = dbuf.stride(0) if M > 1 else F
+    if arg is None:
+        _lib.check(lib.gnn_sage_scatter_agg_f32(
+            dbuf.data_ptr(), ldd, ptr.data_ptr(), slot.data_ptr(), M, k, F, n_prev, dx.data_ptr(),
+            F, ws.data_ptr(), ws.numel(), _lib.stream_handle(dbuf.device)),
+            "gnn_sage_scatter_agg_f32")
+    else:
+        _lib.check(lib.gnn_sage_scatter_agg_maxpool_f32(
+            dbuf.data_ptr(), ldd, arg.data_ptr(), arg.stride(0) if M > 1 else F, ptr.data_ptr(),
+            slot.data_ptr(), M, k, F, n_prev, dx.data_ptr(), F, ws.data_ptr(), ws.numel(),
+            _lib.stream_handle(dbuf.device)), "gnn_sage_scatter_agg_maxpool_f32")
+    return dx
+
+
+def sage_scatter_agg(dbuf: torch.Tensor, tr: SageMapsT, n_prev: int,
+                     out: torch.Tensor | None = None) -> torch.Tensor | None:
+    """The adjoint of ``sage_gather_aggregate(table, idx, 'MEAN')`` (gnn_sage_scatter_agg_f32):
+    dX[t] = sum of dbuf[m] / k over the entries (m, j) with idx[m, j] == t, for the maps
+    ``tr = sage_maps_transpose_nbr(idx, n_prev)``; float32 [n_prev, F] with F = dbuf.shape[1].
+    The gcn-mode twin of ``sage_scatter_concat`` (no centre half) with its contract: rows
+    nobody references are zeros, fp32 sums in slot order, no float atomics, bit-identical from
+    run to run; ``dbuf`` any float32 [M, F] view with 16-B aligned rows, ``out`` a contiguous
+    float32 [n_prev, F] tensor to write. None where the kernel does not take the shape (F not a
+    power of two in [4, 256], k = 0, a misaligned view)."""
+    return _scatter_agg(dbuf, None, tr, n_prev, out)
+
+
+def sage_scatter_agg_maxpool(dbuf: torch.Tensor, arg: torch.Tensor, tr: SageMapsT, n_prev: int,
+                             out: torch.Tensor | None = None) -> torch.Tensor | None:
+    """The adjoint of ``sage_gather_aggregate_arg`` (gnn_sage_scatter_agg_maxpool_f32):
+    dX[t, f] = sum over the entries (m, j) of t of (dbuf[m, f] if arg[m, f] == j else 0), for
+    the maps ``tr = sage_maps_transpose_nbr(idx, n_prev)``. The mask selects (a non-finite
+    gradient at a slot that did not win reaches nobody). Everything else is
+    ``sage_scatter_agg``'s; ``arg``: a uint8 [M, F] view with unit column stride and rows of
+    whole 4-B words. None where the kernel does not take the shape (the widths of
+    ``sage_scatter_agg``, k outside [1, 255], a misaligned view)."""
+    if arg is None:
+        raise TypeError("arg must be a uint8 [M, F] tensor")
+    return _scatter_agg(dbuf, arg, tr, n_prev, out)
+
+
 def sage_train_layer_supported(table: torch.Tensor, weight: torch.Tensor, k: int,
-                               agg: str = 'MEAN') -> bool:
+                               agg: str = 'MEAN', gcn: bool = False) -> bool:
     """Whether the training SageLayer (graphsage._SageTrainLayerFn; ``agg`` 'MAXPOOL':
     graphsage._SageMaxPoolTrainLayerFn) runs on its own kernels for an [n, F] table, an [H, 2F]
     weight and k neighbours per row: ``gcn_transform`` takes (2F, H) and ``sage_scatter_concat``
-    takes F; for 'MAXPOOL' also ``sage_gather_concat_arg`` takes (F, k) and the table's rows."""
+    takes F; for 'MAXPOOL' also ``sage_gather_concat_arg`` takes (F, k) and the table's rows.
+    ``gcn=True`` (graphsage._SageGcnTrainLayerFn): the weight is [H, F], ``gcn_transform`` takes
+    (F, H), ``sage_scatter_agg`` takes F, and for 'MAXPOOL' ``sage_gather_aggregate_arg`` takes
+    (F, k) and the table's rows."""
     if agg not in ('MEAN', 'MAXPOOL'):
         return False
     if (not table.is_cuda or not weight.is_cuda or table.dim() != 2 or weight.dim() != 2
@@ -1928,12 +2120,14 @@ def sage_train_layer_supported(table: torch.Tensor, weight: torch.Tensor, k: int
         return False
     F, (H, K) = table.shape[1], weight.shape
     lib = _lib.load()
-    ok = bool(K == 2 * F and lib.gnn_gcn_transform_supported(K, H)
+    ok = bool(K == (F if gcn else 2 * F) and lib.gnn_gcn_transform_supported(K, H)
               and (TRANSFORM_WIDE_MFMA or not (H == 256 and K > 64))
               and lib.gnn_sage_scatter_concat_supported(F))
     if ok and agg == 'MAXPOOL':
         vec = 8 if table.dtype == torch.bfloat16 else 4
-        ok = bool(lib.gnn_sage_gather_concat_arg_supported(F, k) and F % vec == 0
+        sup = (lib.gnn_sage_gather_aggregate_arg_supported if gcn else
+               lib.gnn_sage_gather_concat_arg_supported)
+        ok = bool(sup(F, k) and F % vec == 0
                   and table.stride(1) == 1 and table.stride(0) % vec == 0
                   and table.data_ptr() % 16 == 0)
     return ok

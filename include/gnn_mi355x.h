@@ -1018,6 +1018,72 @@ int gnn_sage_scatter_concat_maxpool_f32(const float* dbuf, int64_t ldd, const ui
                                         int64_t workspace_bytes, void* stream);
 
 /*
+ * The gcn-mode SageLayer (GraphSAGE(.., gcn=True): GraphSAGE/GraphSAGE.py:13-14 feeds the
+ * aggregate ALONE into Linear(F, H); the sampler puts each node among its own neighbours,
+ * GraphSAGE/data_utils.py:95-96). No centre half anywhere: the buffers are [M, F], and the
+ * M k contributions of a layer are numbered as slots e = m k + j (row e / k, column e % k,
+ * target idx[e / k, e % k]).
+ *
+ * gnn_sage_gather_aggregate_live_f32 / _bf16: gnn_sage_gather_aggregate_f32 / _bf16 in mode
+ *   GNN_SAGE_MEAN or GNN_SAGE_MAXPOOL (any other mode: GNN_E_ARG) over rows
+ *   [0, min(*live, M)) (live: a DEVICE int64 row count, NULL = M), the contract of
+ *   gnn_sage_gather_concat_live_f32: rows from *live on are neither read nor written.
+ * gnn_sage_gather_aggregate_arg_f32 / _bf16: gnn_sage_gather_concat_arg_f32 / _bf16 without
+ *   self_idx / self_out / ld_self:
+ *     out[m, f] = table[idx[m, arg[m, f]], f],  arg[m, f] = the winning slot (uint8)
+ *   with the same order (first maximum, a NaN first), the value AT the stored slot, the same
+ *   shapes (gnn_sage_gather_aggregate_arg_supported(feat, k): feat a power of two in [4, 256],
+ *   [8, 256] for bf16, 1 <= k <= 255, else GNN_E_UNSUPPORTED), alignment (GNN_E_ALIGN) and
+ *   error flag.
+ * gnn_sage_maps_transpose_nbr: gnn_sage_maps_transpose of the neighbour map alone: ptr (int64
+ *   [n_prev + 1]) and slot (int32 [M k]) -- numpy's stable argsort of idx.ravel() with its
+ *   bincount / cumsum, bit for bit. M k >= 2^31 or n_prev >= 2^31 - 1: GNN_E_UNSUPPORTED (the
+ *   workspace query returns it too). An index outside [0, n_prev) sets bit 0 of *err_flag and
+ *   its slot sorts past ptr[n_prev]. workspace: gnn_sage_maps_transpose_nbr_workspace_bytes.
+ * gnn_sage_scatter_agg_f32 (MEAN) / gnn_sage_scatter_agg_maxpool_f32 (MAXPOOL): the adjoint of
+ *   the gcn gather over those maps, dbuf fp32 [M, ldd >= F]:
+ *     MEAN:    dx[t, :F] = (1 / k) sum_{slots (m, j) of t} dbuf[m, 0:F]
+ *     MAXPOOL: dx[t, f]  = sum_{slots (m, j) of t} (arg[m, f] == j ? dbuf[m, f] : 0)   (a select)
+ *   Everything else is gnn_sage_scatter_concat_f32 / _maxpool_f32: the widths
+ *   (gnn_sage_scatter_concat_supported(F)), 1 <= k <= 255 for MAXPOOL, fp32 sums in slot order,
+ *   lists over 256 slots cut into chunks added in chunk order, no float atomics, every row of
+ *   dx stored, alignment and argument checks. workspace:
+ *   gnn_sage_scatter_agg_workspace_bytes / gnn_sage_scatter_agg_maxpool_workspace_bytes(M, k, F).
+ */
+int gnn_sage_gather_aggregate_live_f32(const float* table, int64_t ldt, int64_t n_table,
+                                       const int64_t* idx, int64_t ldi, int64_t M,
+                                       const int64_t* live, int64_t k, int64_t feat, int32_t mode,
+                                       float* out, int64_t ldo, int32_t* err_flag, void* stream);
+int gnn_sage_gather_aggregate_live_bf16(const uint16_t* table, int64_t ldt, int64_t n_table,
+                                        const int64_t* idx, int64_t ldi, int64_t M,
+                                        const int64_t* live, int64_t k, int64_t feat, int32_t mode,
+                                        float* out, int64_t ldo, int32_t* err_flag, void* stream);
+int gnn_sage_gather_aggregate_arg_supported(int64_t feat, int64_t k);
+int gnn_sage_gather_aggregate_arg_f32(const float* table, int64_t ldt, int64_t n_table,
+                                      const int64_t* idx, int64_t ldi, int64_t M, int64_t k,
+                                      int64_t feat, float* out, int64_t ldo, uint8_t* arg,
+                                      int64_t lda, int32_t* err_flag, void* stream);
+int gnn_sage_gather_aggregate_arg_bf16(const uint16_t* table, int64_t ldt, int64_t n_table,
+                                       const int64_t* idx, int64_t ldi, int64_t M, int64_t k,
+                                       int64_t feat, float* out, int64_t ldo, uint8_t* arg,
+                                       int64_t lda, int32_t* err_flag, void* stream);
+int64_t gnn_sage_maps_transpose_nbr_workspace_bytes(int64_t M, int64_t k);
+int gnn_sage_maps_transpose_nbr(const int64_t* idx, int64_t ldi, int64_t M, int64_t k,
+                                int64_t n_prev, int64_t* ptr, int32_t* slot, int32_t* err_flag,
+                                void* workspace, int64_t workspace_bytes, void* stream);
+int64_t gnn_sage_scatter_agg_workspace_bytes(int64_t M, int64_t k, int64_t feat);
+int gnn_sage_scatter_agg_f32(const float* dbuf, int64_t ldd, const int64_t* ptr,
+                             const int32_t* slot, int64_t M, int64_t k, int64_t feat,
+                             int64_t n_prev, float* dx, int64_t ldx, void* workspace,
+                             int64_t workspace_bytes, void* stream);
+int64_t gnn_sage_scatter_agg_maxpool_workspace_bytes(int64_t M, int64_t k, int64_t feat);
+int gnn_sage_scatter_agg_maxpool_f32(const float* dbuf, int64_t ldd, const uint8_t* arg,
+                                     int64_t lda, const int64_t* ptr, const int32_t* slot,
+                                     int64_t M, int64_t k, int64_t feat, int64_t n_prev, float* dx,
+                                     int64_t ldx, void* workspace, int64_t workspace_bytes,
+                                     void* stream);
+
+/*
  * Hashed element dropout fused with a row gather, replacing F.dropout(x, p, training) at
  * GAT/models/GAT.py:15,17 in training (and its backward): r = idx ? idx[i] : i,
  * out[i, c] = x[r, c] / (1 - p) when the (seed, key, c) hash clears p (common.hpp

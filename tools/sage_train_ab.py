@@ -27,6 +27,18 @@ over a random fp32 table: ``sage_gather_concat_arg`` against the three launches 
 half with its zero table, row-id and column tensors, the centre rows' ``_scatter_rows``, and
 their sum), plus the bytes each side keeps for the backward (uint8 against int64 winners).
 
+--gcn: the gcn-mode layers (GraphSAGE(.., gcn=True): relu(W . agg), the sampler's maps of width
+fanout + 1; graphsage._SageGcnTrainLayerFn / _fused_gcn_layer, switch graphsage.SAGE_GCN_FUSED)
+by the same protocol, MEAN and MAXPOOL in one process (--agg is not read): the supervised and
+the unsupervised training step, and the inference forward on a PENDING batch (sample_batch(...,
+sync=False): with the switch off the forward reads the frontier size back, with it on it does
+not), each over an fp32 and a bf16 table with the switch off and on, the four sides alternated.
+Per aggregator it also counts the layer-0 outputs whose ReLU passes on one side only (the two
+sides' GEMMs round differently) and compares the new adjoint alone with the path it replaces at
+the second tower's layer-1 shape.
+
+    python tools/sage_train_ab.py --gcn --out profiles/sage_gcn_ab_cfg4.json
+
 Each comparison also records that both sides compute the same numbers at this size: the largest
 difference of every weight gradient (one step per side) and of the scatter's output, over the
 largest magnitude of the previous path's.
@@ -67,6 +79,8 @@ def main():
     ap.add_argument("--seeds", type=int, default=8192)
     ap.add_argument("--seconds", type=float, default=1.0, help="timed work per side, at least")
     ap.add_argument("--agg", choices=("MEAN", "MAXPOOL"), default="MEAN")
+    ap.add_argument("--gcn", action="store_true",
+                    help="the gcn-mode layers (graphsage.SAGE_GCN_FUSED), MEAN and MAXPOOL")
     ap.add_argument("--out", required=True)
     args = ap.parse_args()
     n, e = (1_000_000, 10_000_000) if args.small else (10_000_000, 100_000_000)
@@ -101,6 +115,8 @@ def main():
     seeds = torch.randperm(n_conn, device=dev, generator=gen)[:B]
     ctx_b = S.sample_contexts(adj, seeds, WINDOW, seed=0)
     neg_b = S.sample_negatives(ctx_b, n_conn, K, seed=0)  # among the nodes with neighbours
+    if args.gcn:
+        return gcn_ab(args, res, write, adj, seeds, ctx_b, neg_b, table, table16, gen)
     pu = S.sample_unsupervised_batch(adj, seeds, fanouts, WINDOW, K, seed=1, contexts=ctx_b,
                                      negatives=neg_b)
     ps = S.sample_batch(adj, seeds, fanouts, seed=1)
@@ -261,6 +277,141 @@ def main():
         "scatter_vs_parent_max_abs_diff_over_max_abs": agree, **kern}
     print(json.dumps({"second_tower_layer1": res["second_tower_layer1"]}), flush=True)
     write()
+
+
+def gcn_ab(args, res, write, adj, seeds, ctx_b, neg_b, table, table16, gen):
+    """--gcn: graphsage.SAGE_GCN_FUSED off / on, both aggregators, on the dataset main() built."""
+    import torch
+    import torch.nn.functional as Fn
+    from graphneuralnetwork_amd import _lib, graphsage, ops
+    from graphneuralnetwork_amd import sampler as S
+    from graphneuralnetwork_amd.graphsage import GraphSAGE
+    from spmm_bf16_ab import alternate
+    dev = table.device
+    F = H = args.feat
+    B, fanouts = args.seeds, (25, 10)
+    pu = S.sample_unsupervised_batch(adj, seeds, fanouts, WINDOW, K, seed=1, contexts=ctx_b,
+                                     negatives=neg_b, gcn=True)
+    ps = S.sample_batch(adj, seeds, fanouts, seed=1, gcn=True)
+    # the same batches with their sizes left on the device (the inference forward's input)
+    qu = S.sample_unsupervised_batch(adj, seeds, fanouts, WINDOW, K, seed=1, contexts=ctx_b,
+                                     negatives=neg_b, gcn=True, sync=False)
+    qs = S.sample_batch(adj, seeds, fanouts, seed=1, gcn=True, sync=False)
+    res.update({"gcn": True, "switch": "graphsage.SAGE_GCN_FUSED",
+                "workload": "cfg4" if not args.small else "small",
+                "nodes": adj.n_rows, "edges": 10_000_000 if args.small else 100_000_000, "feat": F, "hidden": H, "seeds": B, "window": WINDOW, "K": K,
+                "fanout": list(fanouts), "map_widths": [k + 1 for k in fanouts],
+                "device": torch.cuda.get_device_name(dev),
+                "library_stamp": _lib.load().gnn_build_stamp().decode(),
+                "centre_tower_layers": list(pu.center.layer_sizes),
+                "second_tower_layers": list(pu.context.layer_sizes),
+                "timing": f"device events around blocks of calls, sides alternated, >= "
+                          f"{args.seconds} s per side; median and min-max over block means"})
+    y_s = torch.randint(0, 3, (B,), device=dev, generator=gen)
+    y_u = pu.labels.to(torch.float32)
+    for agg in ("MEAN", "MAXPOOL"):
+        torch.manual_seed(0)
+        net_u = GraphSAGE(2, F, H, True, agg_func=agg, Unsupervised=True).to(dev)
+        net_s = GraphSAGE(2, F, H, True, agg_func=agg, Unsupervised=False, class_size=3).to(dev)
+
+        def step(net, batch, tab, fused):
+            a = batch.forward_args(tab)
+            a = a if net.Unsupervised else (*a, None, None, None, None, None)
+
+            def fn():
+                graphsage.SAGE_GCN_FUSED = fused
+                net.zero_grad(set_to_none=True)
+                _, second = net(*a)
+                if net.Unsupervised:
+                    Fn.binary_cross_entropy_with_logits(second.squeeze(1), y_u).backward()
+                else:
+                    Fn.cross_entropy(second, y_s).backward()
+            return fn
+
+        def infer(net, batch, tab, fused):
+            a = batch.forward_args(tab)
+            a = a if net.Unsupervised else (*a, None, None, None, None, None)
+
+            def fn():
+                graphsage.SAGE_GCN_FUSED = fused
+                with torch.no_grad():
+                    return net(*a)
+            return fn
+
+        out = res[agg] = {}
+        for name, make, net, batch, iters in (
+                ("supervised_step", step, net_s, ps, 4), ("unsupervised_step", step, net_u, pu, 1),
+                ("supervised_pending_inference", infer, net_s, qs, 4),
+                ("unsupervised_pending_inference", infer, net_u, qu, 1)):
+            net.train(make is step)
+            t = alternate(torch, {"fp32_off": make(net, batch, table, False),
+                                  "fp32_on": make(net, batch, table, True),
+                                  "bf16_off": make(net, batch, table16, False),
+                                  "bf16_on": make(net, batch, table16, True)},
+                          args.seconds, iters)
+            out[name] = compare(t)
+            # the same numbers? one call per side on the fp32 table
+            if make is step:
+                grads = {}
+                for fused in (False, True):
+                    make(net, batch, table, fused)()
+                    grads[fused] = {k_: p.grad.clone() for k_, p in net.named_parameters()}
+                out[name]["grad_max_abs_diff_over_max_abs"] = {
+                    k_: float((grads[True][k_] - g).abs().max() / g.abs().max())
+                    for k_, g in grads[False].items()}
+            else:
+                off, on = (make(net, batch, table, fused)() for fused in (False, True))
+                out[name]["output_max_abs_diff_over_max_abs"] = [
+                    float((a_ - b_).abs().max() / b_.abs().max()) for a_, b_ in zip(on, off)]
+            print(json.dumps({agg: {name: out[name]}}), flush=True)
+            write()
+        # what stands behind a gradient difference above rounding: the two sides run layer 0's
+        # GEMM on different kernels and a ReLU is not continuous, so an element whose
+        # pre-activation is within rounding of zero passes its gradient on one side only
+        with torch.no_grad():
+            flips = {}
+            for name, net, b in (("supervised", net_s, ps), ("unsupervised_centre", net_u, pu.center),
+                                 ("unsupervised_second", net_u, pu.context)):
+                W0 = net.sage_blocks.sage_layer0.weight.weight
+                buf = ops.sage_gather_aggregate(table, b.frontier_nbrs, agg, check=False)
+                h_on = ops.gcn_transform(buf, W0, relu=True)
+                h_off = torch.relu(Fn.linear(buf, W0))
+                flips[name] = {"elements": h_on.numel(),
+                               "passing_on_one_side_only": int(((h_on > 0) != (h_off > 0)).sum()),
+                               "max_abs_diff": float((h_on - h_off).abs().max()),
+                               "max_abs": float(h_off.abs().max())}
+                del buf, h_on, h_off
+            out["layer0_relu_mask"] = flips
+            # the adjoint alone at the second tower's layer-1 shape, against the path it replaces
+            tower = pu.context
+            idx = tower.neigh_maps[-1]
+            n_prev = int(tower.layers[1].numel())
+            M, k = idx.shape
+            dbuf = torch.randn(M, F, device=dev, generator=gen)
+            tr = ops.sage_maps_transpose_nbr(idx, n_prev)
+            lens = tr.ptr[1:] - tr.ptr[:-1]
+            if agg == "MEAN":
+                old = graphsage._scatter_rows(dbuf, idx, n_prev, 1.0 / k)
+                new = ops.sage_scatter_agg(dbuf, tr, n_prev)
+                again = ops.sage_scatter_agg(dbuf, tr, n_prev)
+            else:
+                h = torch.randn(n_prev, F, device=dev, generator=gen)  # layer 0's output stands in
+                _, arg = ops.sage_gather_aggregate_arg(h, idx, check=False)
+                old = graphsage._gcn_maxpool_scatter_torch(dbuf, arg, idx, n_prev)
+                new = ops.sage_scatter_agg_maxpool(dbuf, arg, tr, n_prev)
+                again = ops.sage_scatter_agg_maxpool(dbuf, arg, tr, n_prev)
+            out["second_tower_layer1_scatter"] = {
+                "M": M, "k": k, "n_prev": n_prev, "slots": M * k,
+                "longest_list": int(lens.max()),
+                "lists_split_into_chunks": int((lens > 256).sum()),
+                "vs_parent_max_abs_diff_over_max_abs":
+                    float((new - old).abs().max() / old.abs().max()),
+                "bit_identical_on_rerun": bool(torch.equal(new, again))}
+            del old, new, again, dbuf, tr
+        print(json.dumps({agg: {k_: out[k_] for k_ in ("layer0_relu_mask",
+                                                       "second_tower_layer1_scatter")}}), flush=True)
+        write()
+    graphsage.SAGE_GCN_FUSED = True
 
 
 if __name__ == "__main__":
