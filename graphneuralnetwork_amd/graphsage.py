@@ -23,7 +23,11 @@ Hot path on gfx950:
 * ``gcn=True`` (``relu(W . agg)``, the sampler's maps holding each node among its neighbours):
   the same over the aggregate alone -- inference as one gather-aggregate into an [M, F] buffer
   plus the MFMA GEMM (a pending batch stays pending), training as ``_SageGcnTrainLayerFn``
-  with the adjoint of the gcn gather on the device (``SAGE_GCN_FUSED``).
+  with the adjoint of the gcn gather on the device (``SAGE_GCN_FUSED``);
+* the unsupervised head (GraphSAGE.py:61 ``torch.bmm`` over a permuted operand, and the loop's
+  ``binary_cross_entropy_with_logits``, train_eval.py:113-114) -> ``_SageScoreFn`` and
+  ``unsupervised_loss`` over ``csrc/sage_score.hip``: the second tower's gradient written in its
+  own [B S, H] layout, fixed-order sums, no float atomics (``SAGE_SCORE_FUSED``).
 """
 from __future__ import annotations
 
@@ -32,15 +36,16 @@ from typing import NamedTuple
 import torch
 import torch.nn.functional as F
 from torch import nn
+from torch.autograd.function import once_differentiable
 
 from .graph import from_coo
-from .ops import (_bf16_inference_only, _masked_grad, _transform_or_mm, gather_rows,
-                  gcn_transform, gemm_tn_masked, linear_relu_classify, sage_aggregate,
-                  sage_gather_aggregate, sage_gather_aggregate_arg, sage_gather_concat,
-                  sage_gather_concat_arg, sage_layer, sage_maps_transpose,
-                  sage_maps_transpose_nbr, sage_scatter_agg, sage_scatter_agg_maxpool,
-                  sage_scatter_concat, sage_scatter_concat_maxpool, sage_train_layer_supported,
-                  spmm_forward)
+from .ops import (_bce_takes, _bf16_inference_only, _masked_grad, _score_takes,
+                  _transform_or_mm, bce_logits, gather_rows, gcn_transform, gemm_tn_masked,
+                  linear_relu_classify, sage_aggregate, sage_gather_aggregate,
+                  sage_gather_aggregate_arg, sage_gather_concat, sage_gather_concat_arg,
+                  sage_layer, sage_maps_transpose, sage_maps_transpose_nbr, sage_scatter_agg,
+                  sage_scatter_agg_maxpool, sage_scatter_concat, sage_scatter_concat_maxpool,
+                  sage_score, sage_score_backward, sage_train_layer_supported, spmm_forward)
 
 # the inference SageLayer GEMM relu([self | agg] @ W^T) runs on the hand-written MFMA kernel
 # (gnn_linear_relu_f32). With the split-bf16 arithmetic (the default, ops.set_transform_precision)
@@ -602,6 +607,87 @@ def _sage_train_layer(block, center: Gathered, neigh: Gathered, agg: str = 'MEAN
     return fn.apply(table, W, cidx, idx)
 
 
+# The head of the unsupervised step on the device (csrc/sage_score.hip): the scores of
+# GraphSAGE.py:61 as ``_SageScoreFn`` in place of torch.bmm over a permuted operand, and
+# ``unsupervised_loss`` in place of the training loop's binary_cross_entropy_with_logits.
+# False: torch's bmm and torch's loss everywhere (tools/unsup_head_ab.py times both).
+SAGE_SCORE_FUSED = True
+
+
+class _SageScoreFn(torch.autograd.Function):
+    """scores[b, 0, s] = center[b] . second[b, s] for center [B, H], second [B, S, H]:
+    ``torch.bmm(center.unsqueeze(1), second.permute(0, 2, 1))`` as one launch
+    (``sage_score``). Backward, one launch (``sage_score_backward``): d_second = g * center in
+    the second tower's own [B S, H] layout (no permuted intermediate to copy back) and
+    d_center = sum_s g second in a fixed order; a half nobody asks for is not computed."""
+
+    @staticmethod
+    def forward(ctx, center, second):
+        B, S, H = second.shape
+        z = sage_score(center, second.reshape(B * S, H), S)
+        if z is None:  # _score_fused_ok said the kernel takes these operands
+            raise RuntimeError("the score kernel refused operands it reports as covered")
+        ctx.save_for_backward(center, second)
+        return z.reshape(B, 1, S)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        center, second = ctx.saved_tensors
+        B, S, H = second.shape
+        r = sage_score_backward(g.reshape(B, S), center, second.reshape(B * S, H),
+                                ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        if r is None:
+            raise RuntimeError("the score kernel refused operands it reports as covered")
+        dc, dx = r
+        return dc, None if dx is None else dx.reshape(B, S, H)
+
+
+def _score_fused_ok(center, second) -> bool:
+    """Whether ``_SageScoreFn`` takes center [B, H] and second [B, S, H]: the switch is on, both
+    are fp32 device tensors and the score kernels take the width and the two layouts."""
+    if not (SAGE_SCORE_FUSED and center.is_cuda and second.is_cuda
+            and center.dtype == torch.float32 and second.dtype == torch.float32
+            and center.dim() == 2 and second.dim() == 3 and second.shape[0] == center.shape[0]
+            and second.shape[2] == center.shape[1] and second.is_contiguous()):
+        return False
+    return _score_takes(center, second.reshape(-1, center.shape[1]))
+
+
+class _BceLogitsFn(torch.autograd.Function):
+    """mean binary cross entropy with logits of z [rows, cols] against y (``bce_logits``): the
+    forward launch also writes g = dL/dz, the backward is g times the incoming scalar."""
+
+    @staticmethod
+    def forward(ctx, z, y):
+        loss, g = bce_logits(z, y, want_grad=ctx.needs_input_grad[0])
+        if g is not None:
+            ctx.save_for_backward(g)
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        (g,) = ctx.saved_tensors
+        return g * grad_out, None
+
+
+def unsupervised_loss(scores, labels):
+    """The unsupervised loss of the reference's loop (GraphSAGE/train_eval.py:113-114),
+    ``F.binary_cross_entropy_with_logits(scores.reshape(labels.shape).float(), labels.float())``,
+    as one autograd function over ``bce_logits``: ``scores`` [B, 1, S] or [B, S], ``labels``
+    int64 or float [B, S]; a 0-dim tensor. torch's function where the kernel does not apply
+    (CPU tensors, no elements, other dtypes, a layout it declines, SAGE_SCORE_FUSED off)."""
+    z = scores.reshape(labels.shape)
+    if (SAGE_SCORE_FUSED and z.is_cuda and labels.is_cuda and z.dtype == torch.float32
+            and labels.dtype in (torch.float32, torch.int64) and z.dim() >= 1
+            and z.numel() > 0 and not labels.requires_grad):
+        z2, y2 = z.reshape(-1, z.shape[-1]), labels.reshape(-1, labels.shape[-1])
+        if _bce_takes(z2, y2):
+            return _BceLogitsFn.apply(z2, y2)
+    return F.binary_cross_entropy_with_logits(z.float(), labels.float())
+
+
 class GraphSAGE(nn.Module):
     """GraphSAGE/GraphSAGE.py:23-61 with the same 9-argument forward."""
 
@@ -698,4 +784,7 @@ class GraphSAGE(nn.Module):
                                                 contexts_negatives_neigh_feats_data,
                                                 contexts_negatives_neigh_nodes_map, None, None, None, None, None)
         contexts_negatives_feats_data = contexts_negatives_feats_data.reshape(*contexts_negatives_shape, -1)
+        if _score_fused_ok(center_feats_data, contexts_negatives_feats_data):
+            return center_feats_data, _SageScoreFn.apply(center_feats_data,
+                                                         contexts_negatives_feats_data)
         return center_feats_data, torch.bmm(center_feats_data.unsqueeze(1), contexts_negatives_feats_data.permute(0, 2, 1))

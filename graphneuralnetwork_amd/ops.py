@@ -2133,6 +2133,139 @@ def sage_train_layer_supported(table: torch.Tensor, weight: torch.Tensor, k: int
     return ok
 
 
+# ---------------------------------------------------------------- the unsupervised head
+def _score_rows(t: torch.Tensor, H: int) -> bool:
+    """An fp32 [rows, H] view the score kernels read or write with 16-B accesses."""
+    return (t.stride(1) == 1 and t.data_ptr() % 16 == 0
+            and (t.shape[0] <= 1 or (t.stride(0) % 4 == 0 and t.stride(0) >= H)))
+
+
+def _score_operands(center: torch.Tensor, second: torch.Tensor, S: int):
+    """(B, S, H) of a score call after the dtype and shape checks of ``sage_score``."""
+    if center.dtype != torch.float32 or second.dtype != torch.float32:
+        raise TypeError(f"center and second must be float32 (got {center.dtype}, {second.dtype})")
+    if center.dim() != 2 or second.dim() != 2:
+        raise ValueError("center must be [B, H] and second [B * S, H]")
+    S = int(S)
+    B, H = center.shape
+    if S < 0 or second.shape != (B * S, H):
+        raise ValueError(f"second must be [B * S, H] = [{B * S}, {H}] (got {tuple(second.shape)})")
+    return B, S, H
+
+
+def _score_takes(center: torch.Tensor, second: torch.Tensor) -> bool:
+    """Whether the score kernels take center [B, H] and second [B S, H] (fp32 device tensors):
+    the width, unit stride along H, 16-B aligned rows."""
+    H = center.shape[1]
+    return bool(_lib.load().gnn_sage_score_supported(H)) and (_score_rows(center, H)
+                                                              and _score_rows(second, H))
+
+
+def _bce_takes(z: torch.Tensor, y: torch.Tensor) -> bool:
+    """Whether ``bce_logits`` takes the layouts of z and y (both [rows, cols])."""
+    rows, cols = z.shape
+    return (rows * cols > 0 and z.stride(1) == 1 and y.stride(1) == 1
+            and (rows == 1 or (z.stride(0) >= cols and y.stride(0) >= cols)))
+
+
+def _ld(t: torch.Tensor, width: int) -> int:
+    return t.stride(0) if t.shape[0] > 1 else max(width, 4)
+
+
+def sage_score(center: torch.Tensor, second: torch.Tensor, S: int,
+               out: torch.Tensor | None = None) -> torch.Tensor | None:
+    """The unsupervised head's scores (gnn_sage_score_f32): z[b, s] = center[b] . second[b S + s],
+    float32 [B, S] -- ``torch.bmm(center.unsqueeze(1), second.reshape(B, S, H).permute(0, 2, 1))``
+    (GraphSAGE/GraphSAGE.py:61) without the permuted operand. fp32 sums in a fixed order:
+    bit-identical from run to run. ``center`` [B, H], ``second`` [B S, H]: float32 views with
+    unit stride along H and 16-B aligned rows; ``out``: a contiguous float32 [B, S] tensor to
+    write. None where the kernel does not take the shape (H not a power of two in [4, 256], a
+    stride along H that is not 1, a misaligned view, a pitch that is not a multiple of 4): the
+    caller keeps torch's path."""
+    _require_device(center, second, out)
+    B, S, H = _score_operands(center, second, S)
+    if out is not None and (out.shape != (B, S) or out.dtype != torch.float32
+                            or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous float32 [{B}, {S}] tensor")
+    lib = _lib.load()
+    if not _score_takes(center, second):
+        return None
+    z = out if out is not None else torch.empty((B, S), dtype=torch.float32,
+                                                device=center.device)
+    if B and S:
+        _lib.check(lib.gnn_sage_score_f32(
+            center.data_ptr(), _ld(center, H), second.data_ptr(), _ld(second, H), B, S, H,
+            z.data_ptr(), S, _lib.stream_handle(center.device)), "gnn_sage_score_f32")
+    return z
+
+
+def sage_score_backward(g: torch.Tensor, center: torch.Tensor, second: torch.Tensor,
+                        need_center: bool = True, need_second: bool = True):
+    """The adjoint of ``sage_score`` for g = dL/dz [B, S] (gnn_sage_score_bwd_f32):
+    (d_center [B, H], d_second [B S, H]) with d_second[b S + s] = g[b, s] * center[b] (exactly
+    torch's product, stored in the layout the second tower's last layer takes) and
+    d_center[b] = sum_s g[b, s] second[b S + s], summed in an order fixed by (S, H): no float
+    atomics, bit-identical from run to run. A half that is not needed is neither computed nor
+    allocated (None in its place). None (alone) where the kernel does not take the shape, as
+    ``sage_score``."""
+    _require_device(g, center, second)
+    if g.dtype != torch.float32:
+        raise TypeError(f"g must be float32 (got {g.dtype})")
+    if g.dim() != 2 or g.shape[0] != center.shape[0]:
+        raise ValueError("g must be [B, S]")
+    B, S, H = _score_operands(center, second, g.shape[1])
+    lib = _lib.load()
+    if not _score_takes(center, second):
+        return None
+    if g.stride(1) != 1 or (B > 1 and g.stride(0) < S):
+        g = g.contiguous()
+    f32 = dict(dtype=torch.float32, device=center.device)
+    if need_center:  # at S = 0 (or B = 0) nothing is launched: the empty sums are these zeros
+        dc = torch.empty((B, H), **f32) if B and S else torch.zeros((B, H), **f32)
+    else:
+        dc = None
+    dx = torch.empty((B * S, H), **f32) if need_second else None
+    if B and S and (need_center or need_second):
+        _lib.check(lib.gnn_sage_score_bwd_f32(
+            g.data_ptr(), g.stride(0) if B > 1 else S, center.data_ptr(), _ld(center, H),
+            second.data_ptr(), _ld(second, H), B, S, H, _lib.ptr(dc), H, _lib.ptr(dx), H,
+            _lib.stream_handle(center.device)), "gnn_sage_score_bwd_f32")
+    return dc, dx
+
+
+def bce_logits(z: torch.Tensor, y: torch.Tensor, want_grad: bool = True):
+    """``F.binary_cross_entropy_with_logits(z, y.float())`` (mean) and its gradient in one pass
+    (gnn_bce_logits_f32): (loss, g) with loss a 0-dim float32 tensor and
+    g = (sigmoid(z) - y) / z.numel() shaped as z (None unless ``want_grad``). torch's expression
+    (1 - y) z - logsigmoid(z), evaluated per element in double and summed in double in a fixed
+    order: bit-identical from run to run, z = +-inf / NaN as in torch. ``z``: float32 [rows,
+    cols]; ``y``: float32 or int64 of the same shape (soft labels as they are). None where the
+    kernel does not take the layout (a stride along the columns that is not 1, no elements): the
+    caller keeps torch's function."""
+    _require_device(z, y)
+    if z.dtype != torch.float32:
+        raise TypeError(f"z must be float32 (got {z.dtype})")
+    if y.dtype not in (torch.float32, torch.int64):
+        raise TypeError(f"y must be float32 or int64 (got {y.dtype})")
+    if z.dim() != 2 or y.shape != z.shape:
+        raise ValueError("z and y must be [rows, cols] of one shape")
+    rows, cols = z.shape
+    if not _bce_takes(z, y):
+        return None
+    lib = _lib.load()
+    dev = z.device
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    g = torch.empty((rows, cols), dtype=torch.float32, device=dev) if want_grad else None
+    ws = torch.empty(int(lib.gnn_bce_logits_workspace_bytes(rows * cols)), dtype=torch.uint8,
+                     device=dev)
+    _lib.check(lib.gnn_bce_logits_f32(
+        z.data_ptr(), z.stride(0) if rows > 1 else cols, y.data_ptr(),
+        y.stride(0) if rows > 1 else cols, int(y.dtype == torch.int64), rows, cols,
+        loss.data_ptr(), _lib.ptr(g), cols, ws.data_ptr(), ws.numel(),
+        _lib.stream_handle(dev)), "gnn_bce_logits_f32")
+    return loss.reshape(()), g
+
+
 # The fused layer is opt-in (set SAGE_FUSED_MIN_ROWS to the smallest frontier to fuse): at
 # cfg4 it gains 2-3 % on layer 0 (62,479 rows: 110 vs 112 us) and loses on the 8,192-row
 # layer 1 (33 vs 25 us) -- its gathers and MFMAs do not overlap, so it costs about their

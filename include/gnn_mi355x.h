@@ -1273,6 +1273,39 @@ int gnn_pyset_order(const int64_t* keys, int64_t n, int64_t* out, int64_t* n_out
 int gnn_pyset_union_order(const int64_t* a, int64_t na, const int64_t* b, int64_t nb,
                           int64_t* out, int64_t* n_out);
 
+/* ---- the head of the unsupervised GraphSAGE step (sage_score.hip) ----
+ * GraphSAGE/GraphSAGE.py:61 torch.bmm(center.unsqueeze(1), second.permute(0, 2, 1)) and
+ * GraphSAGE/train_eval.py:113-114 binary_cross_entropy_with_logits over its scores.
+ * c is the centre embeddings [B, H] (pitch ldc), x the second tower's embeddings [B S, H]
+ * (row b S + s, pitch ldx), all fp32; row offsets are 64-bit.
+ *   gnn_sage_score_supported(H): 1 for H a power of two in [4, 256], else 0.
+ *   gnn_sage_score_f32: z[b, s] = sum_h c[b, h] x[b S + s, h] (z [B, S], pitch ldz >= S).
+ *   gnn_sage_score_bwd_f32: for g = dL/dz [B, S] (pitch ldg >= S),
+ *     dx[b S + s, :] = g[b, s] c[b, :] (one fp32 product per element, stored in the
+ *     [B S, H] layout) and dc[b, :] = sum_s g[b, s] x[b S + s, :], summed in an order that is
+ *     a function of (S, H) alone. dc or dx may be NULL: that half is skipped together with the
+ *     operand only it reads (x for dc, c for dx); both NULL returns GNN_OK.
+ * c, x, dc, dx: 16-B aligned, pitches >= H and multiples of 4 (else GNN_E_ARG / GNN_E_ALIGN);
+ * an H that is not supported: GNN_E_UNSUPPORTED. B = 0 or S = 0 returns GNN_OK with nothing
+ * launched (at S = 0 dc is not written: its rows are the caller's zeros).
+ *   gnn_bce_logits_f32: loss[0] = the mean over rows x cols elements of torch's
+ *     (1 - y) z - logsigmoid(z), logsigmoid(z) = min(z, 0) - log1p(exp(-|z|)), each element
+ *     evaluated in double (so z = +-inf and NaN behave as in torch), and, where g is not NULL,
+ *     g[i, j] = (sigmoid(z) - y) / (rows cols). y is float32, or int64 when y_is_i64 is set;
+ *     soft labels are taken as they are. `ws`: gnn_bce_logits_workspace_bytes(rows cols) bytes,
+ *     8-B aligned (fewer: GNN_E_ARG). rows or cols < 1: GNN_E_ARG (there is no mean of nothing).
+ * No floating-point atomics in any of these: fixed-order sums, bit-identical from run to run. */
+int gnn_sage_score_supported(int64_t H);
+int gnn_sage_score_f32(const float* c, int64_t ldc, const float* x, int64_t ldx, int64_t B,
+                       int64_t S, int64_t H, float* z, int64_t ldz, void* stream);
+int gnn_sage_score_bwd_f32(const float* g, int64_t ldg, const float* c, int64_t ldc,
+                           const float* x, int64_t ldx, int64_t B, int64_t S, int64_t H,
+                           float* dc, int64_t lddc, float* dx, int64_t lddx, void* stream);
+int64_t gnn_bce_logits_workspace_bytes(int64_t n);
+int gnn_bce_logits_f32(const float* z, int64_t ldz, const void* y, int64_t ldy, int32_t y_is_i64,
+                       int64_t rows, int64_t cols, float* loss, float* g, int64_t ldg, void* ws,
+                       int64_t ws_bytes, void* stream);
+
 /* ---- developer entry (not part of the drop-in surface) ----
  * gnn_dev_spmm_variant_f32: gnn_spmm_csr_f32 at feat == 128 with a compile-time
  * kernel variant (0 shipped: U=4, non-temporal Y stores; 1 U=8; 2 U=2; 3 U=4 and 4 U=8
