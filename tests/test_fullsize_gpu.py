@@ -113,7 +113,9 @@ def test_graphsage_cfg4_full_size(agg):
     the 10M / 100M R-MAT adjacency, the drop-in GraphSAGE(2, 128, 128, MEAN) forward on a
     10M x 128 table (5.1 GB: row offsets pass 2^32 bytes), against the numpy oracle
     (GraphSAGE/GraphSAGE.py:38-53, graph_utils.py:6) on the SAME maps: every seed's embedding
-    and logits within 1e-4, plus a layer-0 gather-mean sample over the table's last rows."""
+    and logits within 1e-4, plus a layer-0 gather sample over the table's last rows under all
+    three aggregators bench.py times there: MEAN within 1e-4, MAXPOOL's values and MAX's argmax
+    indices bit for bit (the sampled forward itself stays MEAN)."""
     from graphneuralnetwork_amd.graphsage import GraphSAGE
     from graphneuralnetwork_amd.ops import sage_gather_aggregate
     from graphneuralnetwork_amd.rmat import rmat_edges
@@ -149,8 +151,15 @@ def test_graphsage_cfg4_full_size(agg):
     idx = rng.integers(0, n, (4096, 10))
     idx[:64] = n - 1 - np.arange(640).reshape(64, 10)
     idx[64:96] = (1 << 32) // (4 * F) + np.arange(320).reshape(32, 10)
-    got = sage_gather_aggregate(table, torch.from_numpy(idx).to(dev), agg).cpu().numpy()
+    idx_t = torch.from_numpy(idx).to(dev)
+    got = sage_gather_aggregate(table, idx_t, agg).cpu().numpy()
     close(got, c_oracle.sage_gather(tn, idx, agg))
+    # the other two aggregators bench.py times on this table, over the same rows: the value
+    # max-pool is a selection (bit-exact), and so are MAX's argmax indices
+    got = sage_gather_aggregate(table, idx_t, "MAXPOOL").cpu().numpy()
+    assert np.array_equal(got, c_oracle.sage_gather(tn, idx, "MAXPOOL"))
+    got = sage_gather_aggregate(table, idx_t, "MAX").cpu().numpy()
+    assert got.dtype == np.int64 and np.array_equal(got, c_oracle.sage_argmax(tn, idx))
     assert int(batch.frontier.max()) >= (1 << 32) // (4 * F)  # sampled rows past 2^32 bytes too
 
 

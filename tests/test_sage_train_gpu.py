@@ -182,6 +182,22 @@ def test_scatter_one_target_takes_every_slot(dev):
     close_sum(got, _ref_scatter(d, cidx, idx, n_prev), "hub")
 
 
+@pytest.mark.parametrize("slots", [256, 257])
+def test_scatter_list_at_the_chunk_length(dev, slots):
+    """A list of exactly 256 slots (the last one summed by one lane group) and one of 257 (the
+    first one cut into chunks)."""
+    rng = np.random.default_rng(slots)
+    k, F = 3, 64
+    M = 64 if slots == 256 else 65
+    cidx = np.zeros(M, np.int64)
+    idx = np.zeros((M, k), np.int64)
+    idx[64:] = 1  # M = 65: 65 centre + 192 neighbour slots on target 0, 3 on target 1
+    d = rng.standard_normal((M, 2 * F)).astype(np.float32)
+    dx, tr = _run_scatter(dev, torch.from_numpy(d).to(dev), cidx, idx, 2)
+    assert int(tr.ptr[1]) == slots
+    close_sum(dx.cpu().numpy(), _ref_scatter(d, cidx, idx, 2), f"{slots} slots")
+
+
 def test_scatter_is_deterministic(dev):
     rng = np.random.default_rng(12)
     d, cidx, idx, n_prev = _hub_case(rng)
