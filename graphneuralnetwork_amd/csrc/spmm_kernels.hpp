@@ -145,6 +145,26 @@ constexpr int kWavesPerBlock = kBlock / kWave;
 #ifndef GNN_SPMM_SMALL_SPLIT_UNROLL
 #define GNN_SPMM_SMALL_SPLIT_UNROLL 16
 #endif
+// The schedule of a packed task (A/B: tools/lib_ab.py). Every setting
+// leaves each row sum in the same order: Y is bit-identical for all of them.
+#ifndef GNN_SPMM_BIAS_REG
+#define GNN_SPMM_BIAS_REG 1  // 1: a task loads its lane's bias once, not at every row it writes
+#endif
+#ifndef GNN_SPMM_LEAN
+// 1: fewer instructions and registers per edge -- a task's index, edge base and loop counters
+// as scalars, its edgeless rows as a scalar mask, one compare per edge for the row-end test,
+// the hub / non-hub row address from a sign mask (masked_row). The fp32 F = 128 instance fits
+// 64 VGPRs with it (8 waves per SIMD; tools/kernel_resources.py)
+#define GNN_SPMM_LEAN 1
+#endif
+#ifndef GNN_SPMM_RING
+// 1: a ring of U row buffers per slot -- the row of edge e + U is requested when edge e is
+// consumed, across batch, chunk and row boundaries; 0: request U rows, wait for all, repeat
+#define GNN_SPMM_RING 0
+#endif
+#ifndef GNN_SPMM_PREFETCH
+#define GNN_SPMM_PREFETCH 0  // ring only: the next (col, val) chunk loaded one chunk ahead
+#endif
 #ifndef GNN_SPMM_LDS_PAD
 #define GNN_SPMM_LDS_PAD 0  // A/B: dynamic LDS per workgroup to cap workgroups per CU
 #endif
@@ -217,6 +237,33 @@ __device__ __forceinline__ int slot_lane_i(int v, int base, int stride, int grp)
 template <int LPR>
 __device__ __forceinline__ float slot_lane_f(float v, int base, int stride, int grp) {
   return __int_as_float(slot_lane_i<LPR>(__float_as_int(v), base, stride, grp));
+}
+
+// v, the same in every lane of the wave, as a scalar (an SGPR, not a register per lane)
+__device__ __forceinline__ int wave_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ int64_t wave_uniform(int64_t v) {
+  const uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<int>(v));
+  const uint32_t hi = __builtin_amdgcn_readfirstlane(static_cast<int>(v >> 32));
+  return static_cast<int64_t>((static_cast<uint64_t>(hi) << 32) | lo);
+}
+
+// Row ce of x -- for HUB and ce < 0, row -1-ce of xh -- seen from xs = x + the lane's offset
+// in a row; dbase = xh - x in bytes, dld = ldh - ldx. The table is picked with the sign mask
+// of ce, not with per-lane selects between 64-bit scalars (four moves and four selects per
+// edge in a kernel that is bound by the instructions it issues).
+template <bool HUB, typename XT>
+__device__ __forceinline__ const XT* masked_row(const XT* xs, int64_t ldx, int64_t dbase,
+                                                int64_t dld, int ce) {
+  if constexpr (!HUB) {
+    return xs + static_cast<int64_t>(ce) * ldx;
+  } else {
+    const int m = ce >> 31;  // -1: a row of xh
+    const int64_t mm = m;
+    const int64_t row = static_cast<uint32_t>(ce ^ m);  // ce, or -1 - ce
+    // (pointer arithmetic, not integers: the loads stay global_load, not flat_load)
+    const char* base = reinterpret_cast<const char*>(xs) + (mm & dbase);
+    return reinterpret_cast<const XT*>(base) + row * (ldx + (mm & dld));
+  }
 }
 
 // acc[ch] += sum_{e in [beg, end)} val[e] * x[col[e]][(ch*LPR + sub)*VW .. +VW)
@@ -367,6 +414,32 @@ __device__ __forceinline__ void store_slot_row(float* __restrict__ out,
   }
 }
 
+// The same epilogue with the lane's bias already in registers (bv; has_bias wave-uniform):
+// the row write issues no load of its own unless it accumulates, so it does not have to wait
+// for the gathers in flight behind which that load would queue (vmcnt retires in order).
+template <int VW, int LPR, int NCH, bool NT>
+__device__ __forceinline__ void store_slot_row_reg(float* __restrict__ out,
+                                                   const typename Vec<VW>::T (&bv)[NCH],
+                                                   bool has_bias, int64_t feat, uint32_t flags,
+                                                   int sub, typename Vec<VW>::T (&acc)[NCH]) {
+#pragma unroll
+  for (int ch = 0; ch < NCH; ++ch) {
+    const int64_t f = static_cast<int64_t>(ch * LPR + sub) * VW;
+    if (f >= feat) continue;
+    typename Vec<VW>::T r = acc[ch];
+    if (flags & GNN_EPI_ACCUMULATE) r += vload<VW>(out + f);
+    if (has_bias) r += bv[ch];
+    if (flags & (GNN_EPI_RELU | GNN_EPI_ELU)) {
+#pragma unroll
+      for (int i = 0; i < VW; ++i) vset(r, i, act_apply(vget(r, i), flags));
+    }
+    if (NT)
+      nt_store<VW>(out + f, r);
+    else
+      vstore<VW>(out + f, r);
+  }
+}
+
 // Rows with at most one edge, pre-resolved by the plan (small_col -1 = no edge): EPI x SU
 // rows per wave, one per slot and unroll step, all SU loads issued before the stores.
 template <int VW, int LPR, int NCH, bool NT, int SU, typename XT = float, typename HT = XT>
@@ -416,13 +489,20 @@ __device__ __forceinline__ void small_rows(const SpmmParamsT<XT, HT>& P, int64_t
 // than LPR neighbour rows in flight.
 template <int VW, int LPR, int NCH, int U, bool NT, bool HUB, int CPL = 1, typename XT = float,
           typename HT = XT>
-__device__ __forceinline__ void packed_rows(const SpmmParamsT<XT, HT>& P, int64_t t, int lane) {
+__device__ __forceinline__ void packed_rows(const SpmmParamsT<XT, HT>& P, int64_t t_wave,
+                                            int lane) {
   typedef Fetch<VW, HUB, XT, HT> FX;
   constexpr int EPI = kWave / LPR;
   constexpr int CH = LPR * CPL;  // edges per slot chunk
   static_assert(CH % U == 0, "a batch of U edges never straddles a chunk");
+  constexpr bool kRing = GNN_SPMM_RING && CPL == 1;
+  constexpr bool kLean = GNN_SPMM_LEAN || kRing;
+  constexpr bool kBiasReg = GNN_SPMM_BIAS_REG != 0;
   const int sub = lane & (LPR - 1);
   const int grp = lane / LPR;
+  // kLean: the task index as a scalar (the compiler cannot see that threadIdx.x >> 6 is the
+  // same in every lane), so the task's rows, edge base and loop counters live in SGPRs
+  const int64_t t = kLean ? wave_uniform(t_wave) : t_wave;
   const int32_t rb = P.task_row[2 * t];
   const int32_t re = P.task_row[2 * t + 1];
   // a task outside the contract (1..kTaskRows rows inside [0, n_rows)) is skipped, never read
@@ -432,7 +512,7 @@ __device__ __forceinline__ void packed_rows(const SpmmParamsT<XT, HT>& P, int64_
   const int64_t e0 = P.rowptr[rb];
   // lane l < nr: start of row rb + l relative to e0; lanes >= nr: the task's end
   const int rp = static_cast<int>(P.rowptr[rb + min(lane, nr)] - e0);
-  const int E = __shfl(rp, nr, kWave);
+  const int E = kLean ? wave_uniform(__shfl(rp, nr, kWave)) : __shfl(rp, nr, kWave);
   // slot g takes rows [sb, se): the first row whose (edges + rows) prefix reaches g/EPI of
   // the task's, found by a ballot over the row lanes
   int sb = 0, se = nr;
@@ -449,14 +529,37 @@ __device__ __forceinline__ void packed_rows(const SpmmParamsT<XT, HT>& P, int64_
   }
   int cur = sb;                                   // the row being accumulated
   int cur_end = __shfl(rp, min(cur + 1, nr), kWave);  // its end (slot-uniform)
+  // kLean: a slot that is out of rows holds kNever there, so that the test in front of every
+  // edge is one compare (the last flush asks for kNever - 1: no row ends that late)
+  constexpr int kNever = 0x7fffffff;
+  if constexpr (kLean) cur_end = cur < se ? cur_end : kNever;
   const int es = __shfl(rp, sb, kWave);          // the slot's edge range [es, ee)
   const int ee = __shfl(rp, se, kWave);
-  int cur_beg = es;                               // its start (slot-uniform, no shuffle later)
+  [[maybe_unused]] int cur_beg = es;              // its start (slot-uniform, no shuffle later)
+  // kLean: which rows of the task have no edge, as a wave-uniform mask (bit = row) in place
+  // of the per-lane cur_beg. The shuffle stands on its own, in front of the test of the lane:
+  // inside `lane < nr && ...` it would run with the lanes >= nr masked off, and row nr - 1
+  // reads lane nr
+  [[maybe_unused]] uint64_t empty_rows = 0;
+  if constexpr (kLean) {
+    const int rp_next = __shfl_down(rp, 1, kWave);
+    empty_rows = __ballot(lane < nr && rp_next == rp);
+  }
   const bool skip_empty = (P.flags & GNN_EPI_SKIP_EMPTY) != 0;
   const uint32_t epi = P.flags & (GNN_EPI_RELU | GNN_EPI_ELU | GNN_EPI_ACCUMULATE);
   typename Vec<VW>::T acc[NCH];
 #pragma unroll
   for (int ch = 0; ch < NCH; ++ch) acc[ch] = vzero<VW>();
+  // kBiasReg: the lane's bias, loaded once per task (it does not change during the launch)
+  [[maybe_unused]] typename Vec<VW>::T bv[kBiasReg ? NCH : 1];
+  const bool has_bias = P.bias != nullptr;
+  if constexpr (kBiasReg) {
+#pragma unroll
+    for (int ch = 0; ch < NCH; ++ch) {
+      const int64_t f = static_cast<int64_t>(ch * LPR + sub) * VW;
+      bv[ch] = (has_bias && f < P.feat) ? vload<VW>(P.bias + f) : vzero<VW>();
+    }
+  }
 
   // write every row of the slot that ends at or before edge position `pos` (several when
   // rows without edges follow each other). The only shuffle runs outside the divergent
@@ -464,113 +567,214 @@ __device__ __forceinline__ void packed_rows(const SpmmParamsT<XT, HT>& P, int64_
   // usually in another slot's lane group) is outside EXEC does not return its value. The
   // row's start is tracked slot-uniformly (the previous row's end), not shuffled.
   auto flush_upto = [&](int pos) {
-    bool need = cur < se && pos >= cur_end;
+    bool need = kLean ? pos >= cur_end : (cur < se && pos >= cur_end);
     while (__ballot(need)) {
       if (need) {
-        const bool empty = cur_beg == cur_end;
-        if (!(empty && skip_empty))
-          store_slot_row<VW, LPR, NCH, NT>(P.y + static_cast<int64_t>(rb + cur) * P.ldy, P.bias,
-                                           P.feat, epi, sub, acc);
+        bool empty;
+        if constexpr (kLean) empty = (empty_rows >> cur) & 1;
+        else empty = cur_beg == cur_end;
+        if (!(empty && skip_empty)) {
+          float* out = P.y + static_cast<int64_t>(rb + cur) * P.ldy;
+          if constexpr (kBiasReg)
+            store_slot_row_reg<VW, LPR, NCH, NT>(out, bv, has_bias, P.feat, epi, sub, acc);
+          else
+            store_slot_row<VW, LPR, NCH, NT>(out, P.bias, P.feat, epi, sub, acc);
+        }
 #pragma unroll
         for (int ch = 0; ch < NCH; ++ch) acc[ch] = vzero<VW>();
       }
       cur += need ? 1 : 0;
       const int nxt = __shfl(rp, min(cur + 1, nr), kWave);
-      cur_beg = need ? cur_end : cur_beg;
+      if constexpr (!kLean) cur_beg = need ? cur_end : cur_beg;
       cur_end = need ? nxt : cur_end;
-      need = cur < se && pos >= cur_end;
+      if constexpr (kLean) cur_end = cur < se ? cur_end : kNever;
+      need = kLean ? pos >= cur_end : (cur < se && pos >= cur_end);
     }
   };
 
+  // kLean: what masked_row() needs (unused by the mixed instances, which widen raw halves)
+  [[maybe_unused]] const XT* xs = P.x + sub * VW;
+  [[maybe_unused]] const int64_t dbase =
+      HUB ? reinterpret_cast<intptr_t>(P.xh) - reinterpret_cast<intptr_t>(P.x) : 0;
+  [[maybe_unused]] const int64_t dld = HUB ? P.ldh - P.ldx : 0;
   // every loop below is wave-uniform (the slots' streams differ in length, so the shorter
   // ones idle with their loads masked): the shuffles read rp / c / v from any lane, and a
   // ds_bpermute from a lane outside EXEC would not return its value
   int len = ee - es;
 #pragma unroll
   for (int m = 1; m < kWave; m <<= 1) len = max(len, __shfl_xor(len, m, kWave));
-  flush_upto(es);  // leading rows without edges
-  for (int off = 0; off < len; off += CH) {
-    const int cb = es + off;  // this slot's chunk: lane `sub` holds edges cb + sub + j * LPR
-    int c[CPL];
-    float v[CPL];
-#pragma unroll
-    for (int j = 0; j < CPL; ++j) {
-      c[j] = 0;
-      v[j] = 0.f;
-      if (cb + sub + j * LPR < ee) {
-        c[j] = __builtin_nontemporal_load(P.col + e0 + cb + sub + j * LPR);
-        v[j] = __builtin_nontemporal_load(P.val + e0 + cb + sub + j * LPR);
+  if constexpr (kLean) len = wave_uniform(len);
+  if constexpr (kRing) {
+    // Rolling window: ring buffer u holds the row of stream edge p + u while the batch at p is
+    // consumed, and is refilled with edge p + U + u as soon as its FMA has read it, so U rows
+    // stay in flight across batch, chunk and row ends and a row write costs its store only.
+    // The loop is unrolled by U: every ring index is a constant, the ring lives in registers.
+    //
+    // The task's edges: a wave-uniform base and 32-bit byte offsets (a task holds at most
+    // kTaskRows rows of packed degree: far below 2^30 edges).
+    const char* colp = reinterpret_cast<const char*>(P.col + e0);
+    const char* valp = reinterpret_cast<const char*>(P.val + e0);
+    const int ns = ee - es;                 // its length (len: the longest stream of the wave)
+    typename FX::Raw xv[U][NCH];
+    float w[U];
+    [[maybe_unused]] bool hubrow[FX::kMixed ? U : 1] = {};
+    // (col, val) of the chunk being requested from (c, v: lane `sub` holds its edge `sub`) and
+    // of the one after it (cn, vn). The next chunk is loaded into registers of its own, kAhead
+    // edges before its first request -- a chunk ahead (GNN_SPMM_PREFETCH) or one batch -- and
+    // moved over when the stream reaches it: the wait the compiler places in front of that
+    // move leaves the U row loads issued since in flight. Loading into (c, v) themselves
+    // would put a full drain in front of the next shuffle, in every pass of the loop.
+    constexpr int kAhead = GNN_SPMM_PREFETCH ? CH : U;
+    int c = 0, cn = 0;
+    float v = 0.f, vn = 0.f;
+    auto load_edges = [&](int off, int& cc, float& vv) {  // an edge past the stream's end keeps
+      if (off + sub < ns) {                               // the old value: request() masks it
+        const uint32_t b = 4u * static_cast<uint32_t>(es + off + sub);
+        cc = __builtin_nontemporal_load(reinterpret_cast<const int32_t*>(colp + b));
+        vv = __builtin_nontemporal_load(reinterpret_cast<const float*>(valp + b));
       }
-    }
-    const int n = min(CH, len - off);  // wave-uniform
-    auto batch = [&](int k, auto kc) {  // edges k .. k + U - 1 of the chunk (kc: k when constant)
-      typename FX::Raw xv[U][NCH];
-      float w[U];
-      bool hubrow[FX::kMixed ? U : 1] = {};
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        int ce;
-        float we;
-        if constexpr (CPL == 1) {
+    };
+    auto request = [&](int q, int u) {  // stream edge q -> ring buffer u (q wave-uniform)
 #if GNN_SPMM_READLANE
-          ce = slot_lane_i<LPR>(c[0], (k + u) & (LPR - 1), LPR, grp);
-          we = slot_lane_f<LPR>(v[0], (k + u) & (LPR - 1), LPR, grp);
+      const int ce = slot_lane_i<LPR>(c, q & (LPR - 1), LPR, grp);
+      const float we = slot_lane_f<LPR>(v, q & (LPR - 1), LPR, grp);
 #else
-          const int src = grp * LPR + ((k + u) & (LPR - 1));
-          ce = __shfl(c[0], src, kWave);
-          we = __shfl(v[0], src, kWave);
+      const int src = grp * LPR + (q & (LPR - 1));
+      const int ce = __shfl(c, src, kWave);
+      const float we = __shfl(v, src, kWave);
 #endif
-        } else {  // k is a constant here: the register of edge k + u is known
-          constexpr int K0 = decltype(kc)::value;
-          const int src = grp * LPR + ((K0 + u) % LPR);
-          ce = __shfl(c[(K0 + u) / LPR], src, kWave);
-          we = __shfl(v[(K0 + u) / LPR], src, kWave);
+      const bool ok = q < ns;
+      w[u] = ok ? we : 0.f;
+      if constexpr (FX::kMixed) {
+        const MixedRow<VW, XT, HT> mr(P.x, P.ldx, P.xh, P.ldh, ce);
+        hubrow[u] = mr.hub;
+#pragma unroll
+        for (int ch = 0; ch < NCH; ++ch) {
+          const int64_t f = static_cast<int64_t>(ch * LPR + sub) * VW;
+          xv[u][ch] = mr.load(f, ok && f < P.feat);
         }
-        const bool ok = cb + k + u < ee;
-        w[u] = ok ? we : 0.f;
-        if constexpr (FX::kMixed) {
-          const MixedRow<VW, XT, HT> mr(P.x, P.ldx, P.xh, P.ldh, ce);
-          hubrow[u] = mr.hub;
+      } else {
+        const XT* xr = masked_row<HUB, XT>(xs, P.ldx, dbase, dld, ce);
 #pragma unroll
-          for (int ch = 0; ch < NCH; ++ch) {
-            const int64_t f = static_cast<int64_t>(ch * LPR + sub) * VW;
-            xv[u][ch] = mr.load(f, ok && f < P.feat);
-          }
-        } else {
-          const XT* xr = (HUB && ce < 0) ? P.xh + static_cast<int64_t>(-1 - ce) * P.ldh
-                                         : P.x + static_cast<int64_t>(ce) * P.ldx;
-#pragma unroll
-          for (int ch = 0; ch < NCH; ++ch) {
-            const int64_t f = static_cast<int64_t>(ch * LPR + sub) * VW;
-            xv[u][ch] = (ok && f < P.feat) ? FX::RX::load(xr + f) : FX::zero();
-          }
+        for (int ch = 0; ch < NCH; ++ch) {
+          const int64_t f = static_cast<int64_t>(ch * LPR + sub) * VW;
+          xv[u][ch] = (ok && f < P.feat) ? FX::RX::load(xr + ch * LPR * VW) : FX::zero();
         }
       }
+    };
+    load_edges(0, c, v);
+    if (kAhead == CH && CH < len) load_edges(CH, cn, vn);
+#pragma unroll
+    for (int u = 0; u < U; ++u) request(u, u);
+    flush_upto(es);  // leading rows without edges
+    for (int p = 0; p < len; p += U) {
+      const int q = p + U;  // the batch requested while the batch at p is consumed
+      if ((q & (CH - 1)) == 0) {  // it opens a chunk (wave-uniform, as every branch here)
+        c = cn;
+        v = vn;
+      }
+      if (((q + kAhead) & (CH - 1)) == 0 && q + kAhead < len) load_edges(q + kAhead, cn, vn);
 #pragma unroll
       for (int u = 0; u < U; ++u) {
-        flush_upto(cb + k + u);  // rows that end before this edge (all of them past ee)
+        flush_upto(es + p + u);  // rows that end before this edge (all of them past ee)
 #pragma unroll
         for (int ch = 0; ch < NCH; ++ch)
           acc[ch] += w[u] * FX::f32(xv[u][ch], hubrow[FX::kMixed ? u : 0]);
+        request(q + u, u);
       }
-    };
-    if constexpr (CPL == 1) {
-      for (int k = 0; k < n; k += U) batch(k, std::integral_constant<int, 0>{});
-    } else {  // CH / U batches, unrolled (the register index of each edge is a constant)
-      static_assert(CH / U <= 4, "at most 4 batches per chunk");
-      batch(0, std::integral_constant<int, 0>{});
-      if constexpr (CH / U > 1) {
-        if (U < n) batch(U, std::integral_constant<int, U>{});
+    }
+  } else {
+    flush_upto(es);  // leading rows without edges
+    for (int off = 0; off < len; off += CH) {
+      const int cb = es + off;  // this slot's chunk: lane `sub` holds edges cb + sub + j * LPR
+      int c[CPL];
+      float v[CPL];
+#pragma unroll
+      for (int j = 0; j < CPL; ++j) {
+        c[j] = 0;
+        v[j] = 0.f;
+        if (cb + sub + j * LPR < ee) {
+          c[j] = __builtin_nontemporal_load(P.col + e0 + cb + sub + j * LPR);
+          v[j] = __builtin_nontemporal_load(P.val + e0 + cb + sub + j * LPR);
+        }
       }
-      if constexpr (CH / U > 2) {
-        if (2 * U < n) batch(2 * U, std::integral_constant<int, 2 * U>{});
-      }
-      if constexpr (CH / U > 3) {
-        if (3 * U < n) batch(3 * U, std::integral_constant<int, 3 * U>{});
+      const int n = min(CH, len - off);  // wave-uniform
+      auto batch = [&](int k, auto kc) {  // edges k .. k + U - 1 of the chunk (kc: k when constant)
+        typename FX::Raw xv[U][NCH];
+        float w[U];
+        bool hubrow[FX::kMixed ? U : 1] = {};
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          int ce;
+          float we;
+          if constexpr (CPL == 1) {
+#if GNN_SPMM_READLANE
+            ce = slot_lane_i<LPR>(c[0], (k + u) & (LPR - 1), LPR, grp);
+            we = slot_lane_f<LPR>(v[0], (k + u) & (LPR - 1), LPR, grp);
+#else
+            const int src = grp * LPR + ((k + u) & (LPR - 1));
+            ce = __shfl(c[0], src, kWave);
+            we = __shfl(v[0], src, kWave);
+#endif
+          } else {  // k is a constant here: the register of edge k + u is known
+            constexpr int K0 = decltype(kc)::value;
+            const int src = grp * LPR + ((K0 + u) % LPR);
+            ce = __shfl(c[(K0 + u) / LPR], src, kWave);
+            we = __shfl(v[(K0 + u) / LPR], src, kWave);
+          }
+          const bool ok = cb + k + u < ee;
+          w[u] = ok ? we : 0.f;
+          if constexpr (FX::kMixed) {
+            const MixedRow<VW, XT, HT> mr(P.x, P.ldx, P.xh, P.ldh, ce);
+            hubrow[u] = mr.hub;
+#pragma unroll
+            for (int ch = 0; ch < NCH; ++ch) {
+              const int64_t f = static_cast<int64_t>(ch * LPR + sub) * VW;
+              xv[u][ch] = mr.load(f, ok && f < P.feat);
+            }
+          } else if constexpr (kLean) {
+            const XT* xr = masked_row<HUB, XT>(xs, P.ldx, dbase, dld, ce);
+#pragma unroll
+            for (int ch = 0; ch < NCH; ++ch) {
+              const int64_t f = static_cast<int64_t>(ch * LPR + sub) * VW;
+              xv[u][ch] = (ok && f < P.feat) ? FX::RX::load(xr + ch * LPR * VW) : FX::zero();
+            }
+          } else {
+            const XT* xr = (HUB && ce < 0) ? P.xh + static_cast<int64_t>(-1 - ce) * P.ldh
+                                           : P.x + static_cast<int64_t>(ce) * P.ldx;
+#pragma unroll
+            for (int ch = 0; ch < NCH; ++ch) {
+              const int64_t f = static_cast<int64_t>(ch * LPR + sub) * VW;
+              xv[u][ch] = (ok && f < P.feat) ? FX::RX::load(xr + f) : FX::zero();
+            }
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          flush_upto(cb + k + u);  // rows that end before this edge (all of them past ee)
+#pragma unroll
+          for (int ch = 0; ch < NCH; ++ch)
+            acc[ch] += w[u] * FX::f32(xv[u][ch], hubrow[FX::kMixed ? u : 0]);
+        }
+      };
+      if constexpr (CPL == 1) {
+        for (int k = 0; k < n; k += U) batch(k, std::integral_constant<int, 0>{});
+      } else {  // CH / U batches, unrolled (the register index of each edge is a constant)
+        static_assert(CH / U <= 4, "at most 4 batches per chunk");
+        batch(0, std::integral_constant<int, 0>{});
+        if constexpr (CH / U > 1) {
+          if (U < n) batch(U, std::integral_constant<int, U>{});
+        }
+        if constexpr (CH / U > 2) {
+          if (2 * U < n) batch(2 * U, std::integral_constant<int, 2 * U>{});
+        }
+        if constexpr (CH / U > 3) {
+          if (3 * U < n) batch(3 * U, std::integral_constant<int, 3 * U>{});
+        }
       }
     }
   }
-  flush_upto(0x7fffffff);  // the last row and trailing rows without edges
+  flush_upto(kLean ? kNever - 1 : 0x7fffffff);  // the last row and trailing rows without edges
 }
 
 template <int VW, int LPR, int NCH, int U, bool NT, bool STAGE = false, bool HUB = false,

@@ -73,6 +73,17 @@ VARIANTS = {
     # edge (col, val) moved to the edge slots by v_readlane + select instead of ds_bpermute:
     # slower (cfg2 0.946 vs 0.870 ms, ns 11.87 vs 11.79 ms, profiles/r05u_readlane_*.log)
     "readlane": ["GNN_SPMM_READLANE=1"],
+    # the schedule of a packed task (spmm_kernels.hpp). "parent" pins every
+    # knob to the schedule before them, whatever the defaults are; "parent2" is the same build
+    # again, for the A/A spread. cfg2 (--ordered --bias), profiles/r07_lib_ab_*.log: bias in
+    # registers -2.3 .. -3.1 %, with the lean bookkeeping -3.0 .. -3.3 % (the default); the ring
+    # +5 .. +9 % (slower), 2 % less slow with the next chunk prefetched: both off.
+    "parent": ["GNN_SPMM_BIAS_REG=0", "GNN_SPMM_LEAN=0", "GNN_SPMM_RING=0", "GNN_SPMM_PREFETCH=0"],
+    "parent2": ["GNN_SPMM_BIAS_REG=0", "GNN_SPMM_LEAN=0", "GNN_SPMM_RING=0", "GNN_SPMM_PREFETCH=0"],
+    "breg": ["GNN_SPMM_BIAS_REG=1", "GNN_SPMM_LEAN=0", "GNN_SPMM_RING=0", "GNN_SPMM_PREFETCH=0"],
+    "lean": ["GNN_SPMM_BIAS_REG=1", "GNN_SPMM_LEAN=1", "GNN_SPMM_RING=0", "GNN_SPMM_PREFETCH=0"],
+    "ring": ["GNN_SPMM_BIAS_REG=1", "GNN_SPMM_LEAN=1", "GNN_SPMM_RING=1", "GNN_SPMM_PREFETCH=0"],
+    "ringpf": ["GNN_SPMM_BIAS_REG=1", "GNN_SPMM_LEAN=1", "GNN_SPMM_RING=1", "GNN_SPMM_PREFETCH=1"],
 }
 
 
@@ -94,6 +105,14 @@ def main():
                          "samples of the workload's graph (the cfg4 layer-0 shape)")
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16"],
                     help="element type of the gathered table X")
+    ap.add_argument("--bias", action="store_true",
+                    help="add a bias row, as the GCN layer (and bench.py) does")
+    ap.add_argument("--replay", action="store_true",
+                    help="also bench.spmm_replay per variant (needs --ordered): the step with "
+                         "every gather served by an L2-resident table, the schedule's own cost")
+    ap.add_argument("--equal", action="store_true",
+                    help="compare every variant's full output with the first variant's "
+                         "(torch.equal), print one line each and fail if any differs")
     args = ap.parse_args()
     names = args.variants.split(",")  # "tag" or "tag@seg_len"
     if args.build:
@@ -132,12 +151,44 @@ def main():
 
         def spmm_forward(g_, X_, out=None, seg_len=None):  # noqa: F811 -- same harness
             return sage_gather_aggregate(X_, idx, "MEAN", check=False, out=out)
+    if args.bias and args.op == "spmm":
+        import functools
+        spmm_forward = functools.partial(spmm_forward, bias=torch.randn(F, device=dev))
     ref = spmm_forward(g, X, out=torch.empty_like(Y)).clone()
     libs = {v: ROOT / "graphneuralnetwork_amd" / "lib" / "variants" /
             f"libgnn_{v.split('@')[0]}.so" for v in names}
     seg = {v: int(v.split("@")[1]) for v in names if "@" in v}
     seg.update({f"seg{sl}": int(sl) for sl in args.seg_lens.split(",") if sl})
     names = names + [k for k in seg if k not in names]
+    if args.equal:
+        outs = {}
+        for v in names:
+            _lib.use_variant(libs[v] if v in libs and libs[v].exists() else None)
+            Yv = torch.full_like(Y, float("nan"))
+            spmm_forward(g, X, out=Yv, seg_len=seg.get(v))
+            torch.cuda.synchronize()
+            outs[v] = Yv
+        same = {v: bool(torch.equal(outs[v], outs[names[0]])) for v in names}
+        for v in names:
+            print(json.dumps({"variant": v, "workload": args.workload, "feat": F,
+                              "ordered": args.ordered, "bias": args.bias,
+                              "library": libs[v].name if v in libs and libs[v].exists()
+                              else "default build",
+                              "rows": int(Y.shape[0]), "finite": bool(outs[v].isfinite().all()),
+                              f"torch_equal_to_{names[0]}": same[v]}), flush=True)
+        del outs
+        if not all(same.values()):
+            sys.exit(1)
+    if args.replay and args.op == "spmm":
+        import bench
+        fwd = spmm_forward
+        kw = fwd.keywords if hasattr(fwd, "keywords") else {}
+        for v in names:
+            _lib.use_variant(libs[v] if v in libs and libs[v].exists() else None)
+            rp = bench.spmm_replay(g, X, kw.get("bias"), Y)
+            print(json.dumps({"variant": v, "workload": args.workload, "replay": rp and {
+                k: rp[k] for k in ("as_built_ms", "hub_gathers_in_L2_ms", "all_gathers_in_L2_ms")}}),
+                flush=True)
     times = {v: [] for v in names}
     for r in range(args.rounds):
         for v in names:
