@@ -83,12 +83,6 @@ inline int launch_status() {
 // conflicts. The round-2 layout (row pad of 4 floats, no swizzle) had 2-way conflicts on the
 // fragment reads at K = 16..128 (2.1 conflict cycles per LDS instruction at K = 64,
 // profiles/r02zk_sq_counters_summary.txt).
-#ifdef GNN_TILE_OLD_LDS  // A/B: the round-2 layout (row pad of 4 floats, no swizzle)
-template <int K> struct TileLds {
-  static constexpr int L4 = K / 4 + 1;
-  static __device__ __forceinline__ int swz(int) { return 0; }
-};
-#else
 template <int K> struct TileLds;
 template <> struct TileLds<16> {
   static constexpr int L4 = 4;
@@ -110,7 +104,6 @@ template <> struct TileLds<256> {  // a 1-float4 row pad alone is conflict-free 
   static constexpr int L4 = 65;
   static __device__ __forceinline__ int swz(int) { return 0; }
 };
-#endif
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));

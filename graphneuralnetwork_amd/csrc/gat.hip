@@ -159,13 +159,6 @@ constexpr int gat_small_unroll() {
 #ifndef GNN_GAT_U
 #define GNN_GAT_U 4  // feature-row gathers in flight per lane in phase B (capped at the chunk's slots)
 #endif
-#ifndef GNN_GAT_PIPE
-#define GNN_GAT_PIPE 1  // pipelined chunk loop in gat_csr_kernel (0: plain loop; a depth-2 form,
-                        // two chunks in flight, was slower: profiles/r05b_gat_tasks_ab.log)
-#endif
-#ifndef GNN_GAT_EH
-#define GNN_GAT_EH 1  // segments and mid rows in the edge-head layout (gat_eh_kernel)
-#endif
 #ifndef GNN_GAT_CHUNK
 #define GNN_GAT_CHUNK 8  // edges per phase-A chunk (A/B at cfg3 with the short-row path: 8 > 16 > 32 > 64)
 #endif
@@ -505,15 +498,6 @@ __global__ __launch_bounds__(kGatBlock) void gat_task_kernel(GatParams P) {
         P, t, threadIdx.x & (kWave - 1), el_lds[wid]);
 }
 
-#ifndef GNN_GAT_LDS_PAD
-#define GNN_GAT_LDS_PAD 0  // A/B: dynamic LDS per workgroup to cap workgroups per CU
-#endif
-#ifdef GNN_GAT_WAVES_PER_EU
-#define GNN_GAT_OCC __attribute__((amdgpu_waves_per_eu(GNN_GAT_WAVES_PER_EU)))
-#else
-#define GNN_GAT_OCC
-#endif
-
 // Edge-head layout (heads <= 8 per group, fh = 4 NF): lane (ae, ah) = (edge slot, head) holds
 // head ah's fh features of edge ae's Wh row (NF float4 loads: 8 lanes read a 256-B row at fh = 8),
 // so the score, the online softmax and the weighted sum all run lane-locally: no per-chunk lane
@@ -659,7 +643,7 @@ __global__ __launch_bounds__(kGatBlock) void gat_eh_kernel(GatParams P) {
 }
 
 template <int VW, int LPR, int NCH, int HP, bool SPARSE, int U, int J, bool REC>
-__global__ __launch_bounds__(kGatBlock) GNN_GAT_OCC void gat_csr_kernel(GatParams P) {
+__global__ __launch_bounds__(kGatBlock) void gat_csr_kernel(GatParams P) {
   constexpr int EPI = kWave / LPR;  // phase B: edges per gather instruction
   constexpr int EPP = kWave / HP;   // phase A: edges per pass (lane = edge x head)
   constexpr int C = EPP * J;        // edges per chunk
@@ -712,7 +696,7 @@ __global__ __launch_bounds__(kGatBlock) GNN_GAT_OCC void gat_csr_kernel(GatParam
   }
 
   constexpr int CE = (C + EPI - 1) / EPI;  // gather slots per chunk
-  if constexpr (GNN_GAT_PIPE && J == 1 && NCH == 1 && CE <= 4) {
+  if constexpr (J == 1 && NCH == 1 && CE <= 4) {
     // Pipelined chunk loop: the next chunk's column ids are loaded while this chunk is
     // processed, and this chunk's er entries and Wh rows are issued together, before the
     // softmax arithmetic -- one memory round trip per chunk instead of col -> er -> Wh.
@@ -1137,10 +1121,10 @@ static void launch_gat(const GatParams& P, hipStream_t s) {
   Q.mid_waves = mid_blocks * kGatWaves;
   Q.short_waves = short_blocks * kGatWaves;
   const int64_t blocks = seg_blocks + mid_blocks + short_blocks + small_blocks;
-  // the edge-head layout kernel when a head's features are 1, 2 or 4 float4 (GNN_GAT_EH)
+  // the edge-head layout kernel when a head's features are 1, 2 or 4 float4
   if constexpr (VW == 4 && NCH == 1 && HP <= 8) {
     const int nf = static_cast<int>(P.fh / 4);
-    if (GNN_GAT_EH && P.fh % 4 == 0 && (nf == 1 || nf == 2 || nf == 4) && blocks - short_blocks > 0 &&
+    if (P.fh % 4 == 0 && (nf == 1 || nf == 2 || nf == 4) && blocks - short_blocks > 0 &&
         short_blocks == 0) {
       const dim3 grid(static_cast<unsigned>(blocks));
 #define GNN_EH(NFV)                                                                         \
@@ -1165,22 +1149,19 @@ static void launch_gat(const GatParams& P, hipStream_t s) {
   {
   // er recomputed from the gathered rows: separate instances (the gathering loop's registers
   // do not weigh on the recomputing one), only where the one-chunk loop runs
-  constexpr bool kRec = GNN_GAT_PIPE && J == 1 && NCH == 1 && CE <= 4;
+  constexpr bool kRec = J == 1 && NCH == 1 && CE <= 4;
   if (blocks > 0) {
     if constexpr (kRec) {
       if (P.a_dst != nullptr) {
         hipLaunchKernelGGL((gat_csr_kernel<VW, LPR, NCH, HP, SPARSE, U, J, true>),
-                           dim3(static_cast<unsigned>(blocks)), dim3(kGatBlock), GNN_GAT_LDS_PAD,
-                           s, Q);
+                           dim3(static_cast<unsigned>(blocks)), dim3(kGatBlock), 0, s, Q);
       } else {
         hipLaunchKernelGGL((gat_csr_kernel<VW, LPR, NCH, HP, SPARSE, U, J, false>),
-                           dim3(static_cast<unsigned>(blocks)), dim3(kGatBlock), GNN_GAT_LDS_PAD,
-                           s, Q);
+                           dim3(static_cast<unsigned>(blocks)), dim3(kGatBlock), 0, s, Q);
       }
     } else {
       hipLaunchKernelGGL((gat_csr_kernel<VW, LPR, NCH, HP, SPARSE, U, J, false>),
-                         dim3(static_cast<unsigned>(blocks)), dim3(kGatBlock), GNN_GAT_LDS_PAD, s,
-                         Q);
+                         dim3(static_cast<unsigned>(blocks)), dim3(kGatBlock), 0, s, Q);
     }
   }
   }

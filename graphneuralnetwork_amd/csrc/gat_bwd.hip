@@ -518,9 +518,6 @@ static int dispatch_nodes(const BwdNodeParams& P, const int32_t* lr, const int32
 // own row, held in registers), w_ij and ds_ij. Per edge the node pass reads 4 + 4 feat + 16 H
 // bytes (12 + 4 feat + 2 x 2 lines before) and the row pass writes nothing.
 constexpr int kRowLds = 1152;    // floats of LDS per wave (4.5 KB: 8 waves per SIMD stay)
-#ifndef GNN_BWD_SPLIT_PREP
-#define GNN_BWD_SPLIT_PREP 1  // prep in its own coalesced kernel (0: fused into the row pass)
-#endif
 constexpr int kShortRowsW = 8;   // rows per wave of the short-row class (8 lanes each)
 
 __device__ __forceinline__ void wave_lds_sync() {
@@ -1253,8 +1250,7 @@ extern "C" int gnn_gat_backward_rows_ex_f32(
   // when the head's features are whole float4s, 2^k of them; else fused into the row pass
   const bool rec = a_dst != nullptr;
   const int64_t g4 = fh / 4;
-  const bool split = GNN_BWD_SPLIT_PREP && vec4 && (g4 & (g4 - 1)) == 0 && g4 <= 64 &&
-                     aligned_to(nstat, 16);
+  const bool split = vec4 && (g4 & (g4 - 1)) == 0 && g4 <= 64 && aligned_to(nstat, 16);
   // the upstream dropout mask is applied by the coalesced prep only (the caller masks dy itself
   // for the shapes that fuse the prep into the row pass)
   if (dy_dropout_p > 0.f && (!split || ldo != feat)) return GNN_E_UNSUPPORTED;

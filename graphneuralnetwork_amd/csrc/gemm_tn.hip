@@ -293,11 +293,6 @@ __global__ __launch_bounds__(kTnThreads) void gemm_tn_mfma_kernel(
 // (8 rows apart = 32 banks apart) keeps conflict-free for the two lane halves; the strips are
 // split in registers. 6 x 32 cycles per 16 rows x 32 x 32 outputs against 8 x 64 on the f32
 // MFMA: the kernel is left paced by its HBM reads. C/D lane map as the f32 form's.
-#ifndef GNN_TN_X6_2X2
-#define GNN_TN_X6_2X2 1  // 128 x 128 outputs as 2 x 2 blocks of 32 x 32 per wave (0: 1 x 4;
-                         // tools/tn_ab.py, profiles/r06v_tn_ab.log: DB 0.282 vs 0.325 ms,
-                         // masked 0.331 vs 0.352 at 1M rows)
-#endif
 // DB: D is B (dsum = the column sums of B, taken from B's own staged loads: no third read --
 // the bias gradient next to dW = dY^T Z of a layer trained as (A X) W^T + b).
 // MB: D is a mask H and the kernel multiplies B' = B . [H > 0] * mscale (elementwise, at
@@ -316,7 +311,8 @@ __global__ __launch_bounds__(kTnThreads, 2) void gemm_tn_x6_kernel(
   constexpr int S = 4 / QA;  // k-step streams per tile
   // the 4 waves' share of the QA x QB output blocks: one A block x all B blocks each, or (T22,
   // M = K = 128) 2 x 2 blocks each -- every wave then splits 2 + 2 strips per step, not 1 + 4
-  constexpr bool T22 = GNN_TN_X6_2X2 != 0 && QA == 4 && QB == 4;
+  // (profiles/r06v_tn_ab.log: DB 0.282 vs 0.325 ms, masked 0.331 vs 0.352 at 1M rows)
+  constexpr bool T22 = QA == 4 && QB == 4;
   constexpr int WH = T22 ? 2 : 1, WQ = T22 ? 2 : QB;
   __shared__ float4 sa[kTnRows * PA / 4];
   __shared__ float4 sb[kTnRows * PB / 4];
@@ -488,9 +484,6 @@ __global__ __launch_bounds__(kTnThreads, 2) void gemm_tn_x6_kernel(
 // operand. The 4 waves of a workgroup are summed in wave order through LDS (deterministic),
 // the workgroup partials by gemm_tn_reduce_kernel.
 constexpr int kNarrowK = 16, kNarrowM = 128;
-#ifndef GNN_TN_NARROW_MFMA
-#define GNN_TN_NARROW_MFMA 1  // A/B: 0 = the FMA row walk for M in {64, 128} too
-#endif
 constexpr int kNarrowRowsInFlight = 16;
 
 template <bool DSUM, int MP>
@@ -746,9 +739,6 @@ __global__ __launch_bounds__(256) void gemm_tn_reduce_kernel(const float* __rest
 }
 
 constexpr int64_t kTnBlocks = 512;  // 2 workgroups per CU
-#ifndef GNN_TN_X6  // A/B: 0 = the f32 MFMA kernel in either arithmetic mode
-#define GNN_TN_X6 1
-#endif
 
 static int64_t tn_blocks(int64_t n) {
   const int64_t by_rows = (n + 4 * kTnRows - 1) / (4 * kTnRows);  // >= 4 tiles per block
@@ -764,13 +754,9 @@ static int launch_tn(const float* a, int64_t lda, const float* b, int64_t ldb, c
   int64_t rpb = (n + blocks - 1) / blocks;
   rpb = (rpb + kTnRows - 1) / kTnRows * kTnRows;
   const int64_t stride = M * K + (d || (mask && dsum) ? K : 0);
-#ifndef GNN_TN_FMA  // A/B: the FMA kernel at every shape
   constexpr bool mfma = M >= 64 && K >= 32;
-#else
-  constexpr bool mfma = false;
-#endif
   if constexpr (mfma) {
-    if (GNN_TN_X6 != 0 && g_tf_x6 != 0) {  // the transforms' arithmetic mode (set_precision)
+    if (g_tf_x6 != 0) {  // the transforms' arithmetic mode (set_precision)
       const dim3 grid(static_cast<unsigned>(blocks)), blk(kTnThreads);
       if (mask)  // B' = B . [mask > 0] * mscale (gnn_gemm_tn_masked_f32)
         if (dsum)
@@ -865,7 +851,7 @@ extern "C" int gnn_gemm_tn_f32(const float* a, int64_t lda, const float* b, int6
       else
         hipLaunchKernelGGL((gemm_tn_tiny_kernel<false>), grid, blk, 0, s, a, lda, b, ldb, d, ldd,
                            n, rpb, M, K, part);
-    } else if (GNN_TN_NARROW_MFMA && (m == 64 || m == 128) && aligned_to(a, 16) && lda % 4 == 0) {
+    } else if ((m == 64 || m == 128) && aligned_to(a, 16) && lda % 4 == 0) {
       if (m == 128 && d)
         hipLaunchKernelGGL((gemm_tn_narrow_mfma_kernel<128, true>), grid, blk, 0, s, a, lda, b,
                            ldb, d, ldd, n, rpb, K, part);
@@ -920,7 +906,7 @@ extern "C" int gnn_gemm_tn_f32(const float* a, int64_t lda, const float* b, int6
 // passes exactly where H > 0, scaled by 1 / (1 - p). Wide shapes with m, k >= 64 in the
 // split-bf16 arithmetic only (gnn_gemm_tn_masked_supported); the workspace as gnn_gemm_tn_f32's.
 extern "C" int gnn_gemm_tn_masked_supported(int64_t m, int64_t k) {
-  return GNN_TN_X6 != 0 && g_tf_x6 != 0 && tn_wide(m, k) && m >= 64 && k >= 64;
+  return g_tf_x6 != 0 && tn_wide(m, k) && m >= 64 && k >= 64;
 }
 
 extern "C" int gnn_gemm_tn_masked_f32(const float* a, int64_t lda, const float* b, int64_t ldb,

@@ -52,21 +52,14 @@ template <int K> using ProjLds = TileLds<K>;
 // Each wave stages and reads only its own A tile, so the tile hand-off needs the wave's LDS
 // stores to land before its reads (and its reads before the next tile's stores), not a
 // workgroup barrier: the four waves then drift apart and one's global loads overlap
-// another's MFMAs. GNN_PROJ_BLOCK_SYNC=1 restores the round-2 __syncthreads (A/B).
-#ifndef GNN_PROJ_BLOCK_SYNC
-#define GNN_PROJ_BLOCK_SYNC 0
-#endif
+// another's MFMAs.
 #ifndef GNN_PROJ_DEPTH
 #define GNN_PROJ_DEPTH 1  // A tiles in flight per wave (A/B: 2 and 3 slower, profiles/r03e_proj_ab2.log)
 #endif
 __device__ __forceinline__ void proj_tile_sync() {
-#if GNN_PROJ_BLOCK_SYNC
-  __syncthreads();
-#else
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#endif
 }
 
 // X6 (K = 64; the kernel takes 64 and 128): the products from bf16 MFMAs with three-piece fp32 splits (common.hpp
@@ -106,12 +99,6 @@ __global__ __launch_bounds__(kProjBlock) void gat_project_kernel(
   for (int e = threadIdx.x; e < K * 16; e += kProjBlock)
     w2s[e] = logit_weight(wl, e >> 4, FO, al, heads, fh, e & 15);
   __syncthreads();
-#ifdef GNN_PROJ_B_LDS
-  // B fragments read from LDS at every step (fewer VGPRs, more waves per SIMD)
-  __shared__ float ws[K * FO];
-  for (int e = threadIdx.x; e < K * FO; e += kProjBlock) ws[e] = w[e];
-  __syncthreads();
-#else
   float b[X6 ? 1 : NT][X6 ? 1 : S];  // B fragments: W[q*S + s][16t + r], resident
   float b2[X6 ? 1 : S];
   bf16x8 bx[X6 ? NT + 1 : 1][X6 ? S32 : 1][3];  // X6: pieces of W[q*S + 8 s6 + j][16t + r]
@@ -141,7 +128,6 @@ __global__ __launch_bounds__(kProjBlock) void gat_project_kernel(
 #pragma unroll
     for (int s = 0; s < S; ++s) b2[s] = w2s[(q * S + s) * 16 + r];
   }
-#endif
 
   // A tiles are staged through LDS: a coalesced 16-B-per-lane copy of the wave's 16 rows,
   // then each lane reads its row's quarter (row l & 15, k in [q*S, q*S + S)) as float4s
@@ -281,19 +267,10 @@ __global__ __launch_bounds__(kProjBlock) void gat_project_kernel(
     for (int s = 0; s < S; ++s) {
 #pragma unroll
       for (int j = 0; j < G; ++j) {
-#ifdef GNN_PROJ_B_LDS
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-          acc[j][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(ws[(q * S + s) * FO + 16 * t + r],
-                                                           a[j][s], acc[j][t], 0, 0, 0);
-        acc2[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(w2s[(q * S + s) * 16 + r], a[j][s],
-                                                       acc2[j], 0, 0, 0);
-#else
 #pragma unroll
         for (int t = 0; t < NT; ++t)
           acc[j][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(b[t][s], a[j][s], acc[j][t], 0, 0, 0);
         acc2[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(b2[s], a[j][s], acc2[j], 0, 0, 0);
-#endif
       }
     }
     }

@@ -33,9 +33,6 @@ constexpr int kSageBlock = 256;
 // table, k = 10): 4: 28.5 us, 8: 33.4, 16: 49.9
 #define GNN_SAGE_BF16_U 4
 #endif
-#ifndef GNN_SAGE_LDS_PAD
-#define GNN_SAGE_LDS_PAD 0  // A/B: dynamic LDS per workgroup to cap workgroups per CU
-#endif
 constexpr int kSageWaves = kSageBlock / kWave;
 
 // elements per lane on the vector path (one 16-B load) and slot loads in flight at NCH = 1
@@ -269,12 +266,12 @@ static int launch_sage(const SageArgsT<T>& a) {
   if (blocks > 0x7fffffffLL) return GNN_E_UNSUPPORTED;
   if (GATHER && a.self_idx != nullptr)
     hipLaunchKernelGGL((sage_aggregate_kernel<T, VW, LPR, NCH, MODE, GATHER, U, GATHER>),
-                       dim3(static_cast<unsigned>(blocks)), dim3(kSageBlock), GNN_SAGE_LDS_PAD, a.s,
+                       dim3(static_cast<unsigned>(blocks)), dim3(kSageBlock), 0, a.s,
                        a.src, a.ld_row, a.ld_m, a.n_table, a.idx, a.ldi, a.M, a.k, a.feat, a.out,
                        a.ldo, a.err, a.self_idx, a.self_out, a.ld_self, a.live);
   else
     hipLaunchKernelGGL((sage_aggregate_kernel<T, VW, LPR, NCH, MODE, GATHER, U>),
-                       dim3(static_cast<unsigned>(blocks)), dim3(kSageBlock), GNN_SAGE_LDS_PAD, a.s,
+                       dim3(static_cast<unsigned>(blocks)), dim3(kSageBlock), 0, a.s,
                        a.src, a.ld_row, a.ld_m, a.n_table, a.idx, a.ldi, a.M, a.k, a.feat, a.out,
                        a.ldo, a.err, nullptr, nullptr, 0, a.live);
   return launch_status();
@@ -341,7 +338,7 @@ static int launch_sage_arg(const SageArgsT<T>& a) {
   if (blocks > 0x7fffffffLL) return GNN_E_UNSUPPORTED;
   hipLaunchKernelGGL(
       (sage_aggregate_kernel<T, VW, LPR, 1, kMaxPoolArg, true, SageElem<T>::kU, SELF>),
-      dim3(static_cast<unsigned>(blocks)), dim3(kSageBlock), GNN_SAGE_LDS_PAD, a.s, a.src, a.ld_row,
+      dim3(static_cast<unsigned>(blocks)), dim3(kSageBlock), 0, a.s, a.src, a.ld_row,
       a.ld_m, a.n_table, a.idx, a.ldi, a.M, a.k, a.feat, a.out, a.ldo, a.err, a.self_idx,
       a.self_out, a.ld_self, nullptr, a.arg, a.lda);
   return launch_status();

@@ -42,10 +42,6 @@ __device__ __forceinline__ int64_t uniform_below(uint64_t seed, int64_t pos, int
 }
 
 constexpr int kMaxFanout = 256;
-#ifndef GNN_SAMPLE_THREAD_SERIAL
-#define GNN_SAMPLE_THREAD_SERIAL 0  // A/B: the thread-per-node kernels for every k <= 32
-#endif
-constexpr bool kThreadSerialSample = GNN_SAMPLE_THREAD_SERIAL;
 
 __device__ __forceinline__ int64_t live_rows(int64_t n, const int64_t* n_dev) {
   return n_dev ? min(*n_dev, n) : n;
@@ -57,61 +53,7 @@ __device__ __forceinline__ void sample_fail(int64_t* o, int k, bool self, int64_
   if (self) o[k] = v;
 }
 
-// Fanouts up to KMAX: Floyd's picks stay in registers (both loops unrolled over KMAX with
-// a k predicate, so every array index is a compile-time constant) and the k column loads
-// are issued together at the end. Same draws and picks as the generic path below.
-template <int KMAX>
-__global__ __launch_bounds__(256) void sample_reg_kernel(const int64_t* __restrict__ rowptr,
-                                                         const int32_t* __restrict__ col,
-                                                         int64_t n_graph,
-                                                         const int64_t* __restrict__ nodes,
-                                                         int64_t n, const int64_t* n_dev, int k,
-                                                         int64_t ld, bool self, uint64_t seed,
-                                                         int64_t* __restrict__ out,
-                                                         int32_t* __restrict__ err) {
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (i >= live_rows(n, n_dev)) return;
-  const int64_t v = nodes[i];
-  int64_t* o = out + i * ld;
-  if (v < 0 || v >= n_graph) {
-    atomicOr(err, kSampleErrRange);
-    sample_fail(o, k, self, v);
-    return;
-  }
-  const int64_t b = rowptr[v];
-  const int64_t deg = rowptr[v + 1] - b;
-  if (deg == 0) {
-    atomicOr(err, kSampleErrEmpty);
-    sample_fail(o, k, self, v);
-    return;
-  }
-  int64_t pick[KMAX];
-  if (deg <= k) {  // random.choices: k independent draws
-#pragma unroll
-    for (int j = 0; j < KMAX; ++j)
-      pick[j] = j < k ? uniform_below(seed, i, j, deg) : 0;
-  } else {         // random.sample: Floyd, draw j over [0, deg - k + jj]
-#pragma unroll
-    for (int jj = 0; jj < KMAX; ++jj) {
-      if (jj < k) {
-        const int64_t j = deg - k + jj;
-        const int64_t t = uniform_below(seed, i, j, j + 1);
-        bool seen = false;
-#pragma unroll
-        for (int q = 0; q < jj; ++q) seen |= (pick[q] == t);
-        pick[jj] = seen ? j : t;
-      }
-    }
-  }
-  int64_t c[KMAX];
-#pragma unroll
-  for (int j = 0; j < KMAX; ++j) c[j] = j < k ? col[b + pick[j]] : 0;
-#pragma unroll
-  for (int j = 0; j < KMAX; ++j)
-    if (j < k) o[j] = c[j];
-  if (self) o[k] = v;
-}
-
+// The thread-per-node form (fanouts above 64): the picks live in the output row.
 template <int UNUSED = 0>  // a template: the header is included by two translation units
 __global__ __launch_bounds__(256) void sample_kernel(const int64_t* __restrict__ rowptr,
                                                      const int32_t* __restrict__ col,
@@ -158,7 +100,7 @@ __global__ __launch_bounds__(256) void sample_kernel(const int64_t* __restrict__
 // (draw jj is uniform_below(seed, i, j, j + 1), j = deg - k + jj), only the resolution does
 // ("already picked? then take j"), so every lane draws at once and the resolution runs as k
 // group-wide steps: step jj broadcasts lane jj's draw, the lanes q < jj compare it with their
-// final picks, one ballot decides. Same picks as sample_reg_kernel, bit for bit, with a whole
+// final picks, one ballot decides. Same picks as sample_kernel, bit for bit, with a whole
 // wave per 64 / LPN nodes instead of one thread per node (a thread-serial Floyd over k = 25 took
 // 30.6 us for the 8192 seeds of a cfg4 batch: 128 waves for 256 CUs, profiles/r03ac_cfg4_*).
 // The body of the lane-parallel sampler for one wave: node groups of LPN lanes, node i of
@@ -228,7 +170,7 @@ __device__ __forceinline__ void sample_lane_wave(const int64_t* __restrict__ row
 // (draw jj is uniform_below(seed, i, j, j + 1), j = deg - k + jj), only the resolution does
 // ("already picked? then take j"), so every lane draws at once and the resolution runs as k
 // group-wide steps: step jj broadcasts lane jj's draw, the lanes q < jj compare it with their
-// final picks, one ballot decides. Same picks as sample_reg_kernel, bit for bit, with a whole
+// final picks, one ballot decides. Same picks as sample_kernel, bit for bit, with a whole
 // wave per 64 / LPN nodes instead of one thread per node (a thread-serial Floyd over k = 25 took
 // 30.6 us for the 8192 seeds of a cfg4 batch: 128 waves for 256 CUs, profiles/r03ac_cfg4_*).
 template <int LPN>
@@ -255,30 +197,23 @@ inline void launch_sample(const int64_t* rowptr, const int32_t* col, int64_t n_g
     const int64_t per_block = 4 * (kWave / lpn);
     return dim3(static_cast<unsigned>((n + per_block - 1) / per_block));
   };
-  if (k <= 16 && !kThreadSerialSample) {
+  if (k <= 16) {
     hipLaunchKernelGGL(sample_lane_kernel<16>, lane_grid(16), t, 0, s, rowptr, col, n_graph, nodes,
                        n, n_dev, k, ld, self, seed, out, err);
     return;
   }
-  if (k <= 32 && !kThreadSerialSample) {
+  if (k <= 32) {
     hipLaunchKernelGGL(sample_lane_kernel<32>, lane_grid(32), t, 0, s, rowptr, col, n_graph, nodes,
                        n, n_dev, k, ld, self, seed, out, err);
     return;
   }
-  if (k <= 64 && !kThreadSerialSample) {
+  if (k <= 64) {
     hipLaunchKernelGGL(sample_lane_kernel<64>, lane_grid(64), t, 0, s, rowptr, col, n_graph, nodes,
                        n, n_dev, k, ld, self, seed, out, err);
     return;
   }
-  if (k <= 16)
-    hipLaunchKernelGGL(sample_reg_kernel<16>, g, t, 0, s, rowptr, col, n_graph, nodes, n, n_dev,
-                       k, ld, self, seed, out, err);
-  else if (k <= 32)
-    hipLaunchKernelGGL(sample_reg_kernel<32>, g, t, 0, s, rowptr, col, n_graph, nodes, n, n_dev,
-                       k, ld, self, seed, out, err);
-  else
-    hipLaunchKernelGGL(sample_kernel<0>, g, t, 0, s, rowptr, col, n_graph, nodes, n, n_dev, k, ld,
-                       self, seed, out, err);
+  hipLaunchKernelGGL(sample_kernel<0>, g, t, 0, s, rowptr, col, n_graph, nodes, n, n_dev, k, ld,
+                     self, seed, out, err);
 }
 
 }  // namespace gnn

@@ -75,7 +75,7 @@ extern "C" int gnn_spmm_csr_f32(const int64_t* rowptr, const int32_t* col, const
                                 int64_t n_mid, float* partial, uint32_t flags, void* stream) {
   return spmm_entry(rowptr, col, val, n_rows, x, ldx, feat, bias, y, ldy, seg_len, seg_row,
                     seg_begin, n_seg, long_row, long_seg_ptr, n_long, small_row, small_col,
-                    small_val, n_small, mid_row, n_mid, partial, flags, stream, -1);
+                    small_val, n_small, mid_row, n_mid, partial, flags, stream);
 }
 
 extern "C" int gnn_spmm_csr_hub_f32(const int64_t* rowptr, const int32_t* col_hub,
@@ -91,24 +91,7 @@ extern "C" int gnn_spmm_csr_hub_f32(const int64_t* rowptr, const int32_t* col_hu
   if (xh == nullptr) return GNN_E_ARG;
   return spmm_entry(rowptr, col_hub, val, n_rows, x, ldx, feat, bias, y, ldy, seg_len, seg_row,
                     seg_begin, n_seg, long_row, long_seg_ptr, n_long, small_row, small_col,
-                    small_val, n_small, mid_row, n_mid, partial, flags, stream, -1, xh, ldh);
-}
-
-// ---- developer entry: kernel-variant A/B at one shape (tools/spmm_ab.py) ----
-extern "C" int gnn_dev_spmm_variant_f32(const int64_t* rowptr, const int32_t* col,
-                                        const float* val, int64_t n_rows, const float* x,
-                                        int64_t ldx, int64_t feat, const float* bias, float* y,
-                                        int64_t ldy, int64_t seg_len, const int32_t* seg_row,
-                                        const int64_t* seg_begin, int64_t n_seg,
-                                        const int32_t* long_row, const int32_t* long_seg_ptr,
-                                        int64_t n_long, const int32_t* small_row,
-                                        const int32_t* small_col, const float* small_val,
-                                        int64_t n_small, const int32_t* mid_row, int64_t n_mid,
-                                        float* partial, int32_t variant, void* stream) {
-  if (variant < 0) return GNN_E_ARG;
-  return spmm_entry(rowptr, col, val, n_rows, x, ldx, feat, bias, y, ldy, seg_len, seg_row,
-                    seg_begin, n_seg, long_row, long_seg_ptr, n_long, small_row, small_col,
-                    small_val, n_small, mid_row, n_mid, partial, 0u, stream, variant);
+                    small_val, n_small, mid_row, n_mid, partial, flags, stream, xh, ldh);
 }
 
 // ---- packed row tasks (GCN/GCN.py:43-45, same aggregation): see packed_rows ----
@@ -126,6 +109,6 @@ extern "C" int gnn_spmm_csr_tasks_f32(const int64_t* rowptr, const int32_t* col,
   if (xh == nullptr) ldh = 0;
   return spmm_entry(rowptr, col, val, n_rows, x, ldx, feat, bias, y, ldy, seg_len, seg_row,
                     seg_begin, n_seg, long_row, long_seg_ptr, n_long, nullptr, nullptr, nullptr, 0,
-                    mid_row, n_mid, partial, flags, stream, -1, xh, ldh,
+                    mid_row, n_mid, partial, flags, stream, xh, ldh,
                     task_row != nullptr ? task_row : mid_row, n_task);
 }

@@ -67,12 +67,12 @@ static int spmm_bf16_entry(const int64_t* rowptr, const int32_t* col, const floa
     return spmm_entry<bf16_t, float>(rowptr, col, val, n_rows, as_bf16(x), ldx, feat, bias, y, ldy,
                                      seg_len, seg_row, seg_begin, n_seg, long_row, long_seg_ptr,
                                      n_long, small_row, small_col, small_val, n_small, mid_row,
-                                     n_mid, partial, flags, stream, -1,
+                                     n_mid, partial, flags, stream,
                                      static_cast<const float*>(xh), ldh, task_row, n_task);
   return spmm_entry<bf16_t, bf16_t>(rowptr, col, val, n_rows, as_bf16(x), ldx, feat, bias, y, ldy,
                                     seg_len, seg_row, seg_begin, n_seg, long_row, long_seg_ptr,
                                     n_long, small_row, small_col, small_val, n_small, mid_row,
-                                    n_mid, partial, flags, stream, -1,
+                                    n_mid, partial, flags, stream,
                                     static_cast<const bf16_t*>(xh), ldh, task_row, n_task);
 }
 

@@ -133,40 +133,11 @@ constexpr int kWavesPerBlock = kBlock / kWave;
 #ifndef GNN_SPMM_U
 #define GNN_SPMM_U 4  // slot loads in flight per lane for one-chunk rows (A/B: tools/lib_ab.py)
 #endif
-#ifndef GNN_SPMM_SMALL_SPLIT
-#define GNN_SPMM_SMALL_SPLIT 0
-#endif
 #ifndef GNN_SPMM_NARROW_CH
 #define GNN_SPMM_NARROW_CH 8  // edges per slot chunk in packed tasks of narrow rows (1 = LPR)
 #endif
 #ifndef GNN_SPMM_TASK_U
 #define GNN_SPMM_TASK_U 0  // neighbour rows in flight per slot in packed tasks (0: as GNN_SPMM_U)
-#endif
-#ifndef GNN_SPMM_SMALL_SPLIT_UNROLL
-#define GNN_SPMM_SMALL_SPLIT_UNROLL 16
-#endif
-// The schedule of a packed task (A/B: tools/lib_ab.py). Every setting
-// leaves each row sum in the same order: Y is bit-identical for all of them.
-#ifndef GNN_SPMM_BIAS_REG
-#define GNN_SPMM_BIAS_REG 1  // 1: a task loads its lane's bias once, not at every row it writes
-#endif
-#ifndef GNN_SPMM_LEAN
-// 1: fewer instructions and registers per edge -- a task's index, edge base and loop counters
-// as scalars, its edgeless rows as a scalar mask, one compare per edge for the row-end test,
-// the hub / non-hub row address from a sign mask (masked_row). The fp32 F = 128 instance fits
-// 64 VGPRs with it (8 waves per SIMD; tools/kernel_resources.py)
-#define GNN_SPMM_LEAN 1
-#endif
-#ifndef GNN_SPMM_RING
-// 1: a ring of U row buffers per slot -- the row of edge e + U is requested when edge e is
-// consumed, across batch, chunk and row boundaries; 0: request U rows, wait for all, repeat
-#define GNN_SPMM_RING 0
-#endif
-#ifndef GNN_SPMM_PREFETCH
-#define GNN_SPMM_PREFETCH 0  // ring only: the next (col, val) chunk loaded one chunk ahead
-#endif
-#ifndef GNN_SPMM_LDS_PAD
-#define GNN_SPMM_LDS_PAD 0  // A/B: dynamic LDS per workgroup to cap workgroups per CU
 #endif
 constexpr int kSmallUnroll = GNN_SPMM_SMALL_UNROLL;  // small rows per slot per wave (NCH = 1)
 // per column-chunk count: the unrolled loads stay at ~16 x 16 B per lane
@@ -174,8 +145,6 @@ template <int NCH>
 constexpr int small_unroll() {
   return kSmallUnroll / NCH >= 2 ? kSmallUnroll / NCH : 2;
 }
-constexpr bool kSmallSplit = GNN_SPMM_SMALL_SPLIT;   // small rows in their own launch
-constexpr int kSmallSplitUnroll = GNN_SPMM_SMALL_SPLIT_UNROLL;
 
 template <typename XT = float, typename HT = XT>
 struct SpmmParamsT {
@@ -217,27 +186,6 @@ typedef SpmmParamsT<> SpmmParams;
 
 // rows per packed task: the task's rowptr values (rows + 1) live in one VGPR (lane = row)
 constexpr int kTaskRows = kWave - 1;
-
-#ifndef GNN_SPMM_READLANE
-#define GNN_SPMM_READLANE 0  // A/B: edge (col, val) moved to the slots by v_readlane + select
-#endif
-// v of lane (base + s * stride) & 63 for the calling lane's slot s = lane / LPR (base wave-
-// uniform): EPI scalar lane reads and selects instead of one ds_bpermute round trip through LDS
-template <int LPR>
-__device__ __forceinline__ int slot_lane_i(int v, int base, int stride, int grp) {
-  constexpr int EPI = kWave / LPR;
-  int r = __builtin_amdgcn_readlane(v, base & (kWave - 1));
-#pragma unroll
-  for (int s = 1; s < EPI; ++s) {
-    const int t = __builtin_amdgcn_readlane(v, (base + s * stride) & (kWave - 1));
-    r = grp == s ? t : r;
-  }
-  return r;
-}
-template <int LPR>
-__device__ __forceinline__ float slot_lane_f(float v, int base, int stride, int grp) {
-  return __int_as_float(slot_lane_i<LPR>(__float_as_int(v), base, stride, grp));
-}
 
 // v, the same in every lane of the wave, as a scalar (an SGPR, not a register per lane)
 __device__ __forceinline__ int wave_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
@@ -298,14 +246,9 @@ __device__ __forceinline__ void gather_rows(const int32_t* __restrict__ col,
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int e = k + u * EPI + grp;
-#if GNN_SPMM_READLANE
-        const int ce = slot_lane_i<LPR>(c, k + u * EPI, 1, grp);
-        const float we = slot_lane_f<LPR>(v, k + u * EPI, 1, grp);
-#else
         const int src = e & (kWave - 1);
         const int ce = __shfl(c, src, kWave);
         const float we = __shfl(v, src, kWave);
-#endif
         w[u] = e < n ? we : 0.f;
         if constexpr (FX::kMixed) {
           const MixedRow<VW, XT, HT> mr(x, ldx, xh, ldh, ce);
@@ -331,51 +274,6 @@ __device__ __forceinline__ void gather_rows(const int32_t* __restrict__ col,
         for (int ch = 0; ch < NCH; ++ch)
           acc[ch] += w[u] * FX::f32(xv[u][ch], hubrow[FX::kMixed ? u : 0]);
       }
-    }
-  }
-}
-
-// A/B variant (tools/spmm_ab.py variant 3): the same gather with every neighbour row
-// staged through LDS by LDS-DMA (global_load_lds_dwordx4: per-lane source address, the
-// wave's 1 KiB lands lane-linear at a wave-uniform LDS base) instead of loaded into
-// VGPRs -- the "LDS-staged feature tiles" alternative. Each staged row is read back once
-// by the lane that requested it, so LDS adds a write + read per byte and frees no reuse;
-// measured against the register path in profiles/ (DESIGN.md section 4). VW = 4, NCH = 1.
-template <int LPR, int U>
-__device__ __forceinline__ void gather_rows_lds(const int32_t* __restrict__ col,
-                                                const float* __restrict__ val, int64_t beg,
-                                                int64_t end, const float* __restrict__ x,
-                                                int64_t ldx, int lane, f4& acc, f4* stage) {
-  constexpr int EPI = kWave / LPR;
-  const int sub = lane & (LPR - 1);
-  const int grp = lane / LPR;
-  for (int64_t base = beg; base < end; base += kWave) {
-    const int n = static_cast<int>(min(static_cast<int64_t>(kWave), end - base));
-    int c = 0;
-    float v = 0.f;
-    if (lane < n) {
-      c = __builtin_nontemporal_load(col + base + lane);
-      v = __builtin_nontemporal_load(val + base + lane);
-    }
-    for (int k = 0; k < n; k += EPI * U) {
-      float w[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int e = k + u * EPI + grp;
-        const int ce = __shfl(c, e & (kWave - 1), kWave);
-        const float we = __shfl(v, e & (kWave - 1), kWave);
-        w[u] = we;
-        const float* src = x + static_cast<int64_t>(e < n ? ce : 0) * ldx + sub * 4;
-        __builtin_amdgcn_global_load_lds(
-            (const __attribute__((address_space(1))) void*)src,
-            (__attribute__((address_space(3))) void*)(stage + u * kWave), 16, 0, 0);
-      }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        if (k + u * EPI + grp < n) acc += w[u] * stage[u * kWave + lane];
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // reads done before the next DMA
     }
   }
 }
@@ -495,14 +393,11 @@ __device__ __forceinline__ void packed_rows(const SpmmParamsT<XT, HT>& P, int64_
   constexpr int EPI = kWave / LPR;
   constexpr int CH = LPR * CPL;  // edges per slot chunk
   static_assert(CH % U == 0, "a batch of U edges never straddles a chunk");
-  constexpr bool kRing = GNN_SPMM_RING && CPL == 1;
-  constexpr bool kLean = GNN_SPMM_LEAN || kRing;
-  constexpr bool kBiasReg = GNN_SPMM_BIAS_REG != 0;
   const int sub = lane & (LPR - 1);
   const int grp = lane / LPR;
-  // kLean: the task index as a scalar (the compiler cannot see that threadIdx.x >> 6 is the
-  // same in every lane), so the task's rows, edge base and loop counters live in SGPRs
-  const int64_t t = kLean ? wave_uniform(t_wave) : t_wave;
+  // the task index as a scalar (the compiler cannot see that threadIdx.x >> 6 is the same in
+  // every lane), so the task's rows, edge base and loop counters live in SGPRs
+  const int64_t t = wave_uniform(t_wave);
   const int32_t rb = P.task_row[2 * t];
   const int32_t re = P.task_row[2 * t + 1];
   // a task outside the contract (1..kTaskRows rows inside [0, n_rows)) is skipped, never read
@@ -512,7 +407,7 @@ __device__ __forceinline__ void packed_rows(const SpmmParamsT<XT, HT>& P, int64_
   const int64_t e0 = P.rowptr[rb];
   // lane l < nr: start of row rb + l relative to e0; lanes >= nr: the task's end
   const int rp = static_cast<int>(P.rowptr[rb + min(lane, nr)] - e0);
-  const int E = kLean ? wave_uniform(__shfl(rp, nr, kWave)) : __shfl(rp, nr, kWave);
+  const int E = wave_uniform(__shfl(rp, nr, kWave));
   // slot g takes rows [sb, se): the first row whose (edges + rows) prefix reaches g/EPI of
   // the task's, found by a ballot over the row lanes
   int sb = 0, se = nr;
@@ -529,70 +424,56 @@ __device__ __forceinline__ void packed_rows(const SpmmParamsT<XT, HT>& P, int64_
   }
   int cur = sb;                                   // the row being accumulated
   int cur_end = __shfl(rp, min(cur + 1, nr), kWave);  // its end (slot-uniform)
-  // kLean: a slot that is out of rows holds kNever there, so that the test in front of every
-  // edge is one compare (the last flush asks for kNever - 1: no row ends that late)
+  // a slot that is out of rows holds kNever there, so that the test in front of every edge is
+  // one compare (the last flush asks for kNever - 1: no row ends that late)
   constexpr int kNever = 0x7fffffff;
-  if constexpr (kLean) cur_end = cur < se ? cur_end : kNever;
+  cur_end = cur < se ? cur_end : kNever;
   const int es = __shfl(rp, sb, kWave);          // the slot's edge range [es, ee)
   const int ee = __shfl(rp, se, kWave);
-  [[maybe_unused]] int cur_beg = es;              // its start (slot-uniform, no shuffle later)
-  // kLean: which rows of the task have no edge, as a wave-uniform mask (bit = row) in place
-  // of the per-lane cur_beg. The shuffle stands on its own, in front of the test of the lane:
-  // inside `lane < nr && ...` it would run with the lanes >= nr masked off, and row nr - 1
-  // reads lane nr
-  [[maybe_unused]] uint64_t empty_rows = 0;
-  if constexpr (kLean) {
-    const int rp_next = __shfl_down(rp, 1, kWave);
-    empty_rows = __ballot(lane < nr && rp_next == rp);
-  }
+  // which rows of the task have no edge, as a wave-uniform mask (bit = row). The shuffle stands
+  // on its own, in front of the test of the lane: inside `lane < nr && ...` it would run with
+  // the lanes >= nr masked off, and row nr - 1 reads lane nr
+  const int rp_next = __shfl_down(rp, 1, kWave);
+  const uint64_t empty_rows = __ballot(lane < nr && rp_next == rp);
   const bool skip_empty = (P.flags & GNN_EPI_SKIP_EMPTY) != 0;
   const uint32_t epi = P.flags & (GNN_EPI_RELU | GNN_EPI_ELU | GNN_EPI_ACCUMULATE);
   typename Vec<VW>::T acc[NCH];
 #pragma unroll
   for (int ch = 0; ch < NCH; ++ch) acc[ch] = vzero<VW>();
-  // kBiasReg: the lane's bias, loaded once per task (it does not change during the launch)
-  [[maybe_unused]] typename Vec<VW>::T bv[kBiasReg ? NCH : 1];
+  // the lane's bias, loaded once per task (it does not change during the launch)
+  typename Vec<VW>::T bv[NCH];
   const bool has_bias = P.bias != nullptr;
-  if constexpr (kBiasReg) {
 #pragma unroll
-    for (int ch = 0; ch < NCH; ++ch) {
-      const int64_t f = static_cast<int64_t>(ch * LPR + sub) * VW;
-      bv[ch] = (has_bias && f < P.feat) ? vload<VW>(P.bias + f) : vzero<VW>();
-    }
+  for (int ch = 0; ch < NCH; ++ch) {
+    const int64_t f = static_cast<int64_t>(ch * LPR + sub) * VW;
+    bv[ch] = (has_bias && f < P.feat) ? vload<VW>(P.bias + f) : vzero<VW>();
   }
 
   // write every row of the slot that ends at or before edge position `pos` (several when
   // rows without edges follow each other). The only shuffle runs outside the divergent
   // branch, with the whole wave active: a ds_bpermute whose source lane (here a row index,
-  // usually in another slot's lane group) is outside EXEC does not return its value. The
-  // row's start is tracked slot-uniformly (the previous row's end), not shuffled.
+  // usually in another slot's lane group) is outside EXEC does not return its value.
   auto flush_upto = [&](int pos) {
-    bool need = kLean ? pos >= cur_end : (cur < se && pos >= cur_end);
+    bool need = pos >= cur_end;
     while (__ballot(need)) {
       if (need) {
-        bool empty;
-        if constexpr (kLean) empty = (empty_rows >> cur) & 1;
-        else empty = cur_beg == cur_end;
+        const bool empty = (empty_rows >> cur) & 1;
         if (!(empty && skip_empty)) {
           float* out = P.y + static_cast<int64_t>(rb + cur) * P.ldy;
-          if constexpr (kBiasReg)
-            store_slot_row_reg<VW, LPR, NCH, NT>(out, bv, has_bias, P.feat, epi, sub, acc);
-          else
-            store_slot_row<VW, LPR, NCH, NT>(out, P.bias, P.feat, epi, sub, acc);
+          store_slot_row_reg<VW, LPR, NCH, NT>(out, bv, has_bias, P.feat, epi, sub, acc);
         }
 #pragma unroll
         for (int ch = 0; ch < NCH; ++ch) acc[ch] = vzero<VW>();
       }
       cur += need ? 1 : 0;
       const int nxt = __shfl(rp, min(cur + 1, nr), kWave);
-      if constexpr (!kLean) cur_beg = need ? cur_end : cur_beg;
       cur_end = need ? nxt : cur_end;
-      if constexpr (kLean) cur_end = cur < se ? cur_end : kNever;
-      need = kLean ? pos >= cur_end : (cur < se && pos >= cur_end);
+      cur_end = cur < se ? cur_end : kNever;
+      need = pos >= cur_end;
     }
   };
 
-  // kLean: what masked_row() needs (unused by the mixed instances, which widen raw halves)
+  // what masked_row() needs (unused by the mixed instances, which widen raw halves)
   [[maybe_unused]] const XT* xs = P.x + sub * VW;
   [[maybe_unused]] const int64_t dbase =
       HUB ? reinterpret_cast<intptr_t>(P.xh) - reinterpret_cast<intptr_t>(P.x) : 0;
@@ -603,187 +484,91 @@ __device__ __forceinline__ void packed_rows(const SpmmParamsT<XT, HT>& P, int64_
   int len = ee - es;
 #pragma unroll
   for (int m = 1; m < kWave; m <<= 1) len = max(len, __shfl_xor(len, m, kWave));
-  if constexpr (kLean) len = wave_uniform(len);
-  if constexpr (kRing) {
-    // Rolling window: ring buffer u holds the row of stream edge p + u while the batch at p is
-    // consumed, and is refilled with edge p + U + u as soon as its FMA has read it, so U rows
-    // stay in flight across batch, chunk and row ends and a row write costs its store only.
-    // The loop is unrolled by U: every ring index is a constant, the ring lives in registers.
-    //
-    // The task's edges: a wave-uniform base and 32-bit byte offsets (a task holds at most
-    // kTaskRows rows of packed degree: far below 2^30 edges).
-    const char* colp = reinterpret_cast<const char*>(P.col + e0);
-    const char* valp = reinterpret_cast<const char*>(P.val + e0);
-    const int ns = ee - es;                 // its length (len: the longest stream of the wave)
-    typename FX::Raw xv[U][NCH];
-    float w[U];
-    [[maybe_unused]] bool hubrow[FX::kMixed ? U : 1] = {};
-    // (col, val) of the chunk being requested from (c, v: lane `sub` holds its edge `sub`) and
-    // of the one after it (cn, vn). The next chunk is loaded into registers of its own, kAhead
-    // edges before its first request -- a chunk ahead (GNN_SPMM_PREFETCH) or one batch -- and
-    // moved over when the stream reaches it: the wait the compiler places in front of that
-    // move leaves the U row loads issued since in flight. Loading into (c, v) themselves
-    // would put a full drain in front of the next shuffle, in every pass of the loop.
-    constexpr int kAhead = GNN_SPMM_PREFETCH ? CH : U;
-    int c = 0, cn = 0;
-    float v = 0.f, vn = 0.f;
-    auto load_edges = [&](int off, int& cc, float& vv) {  // an edge past the stream's end keeps
-      if (off + sub < ns) {                               // the old value: request() masks it
-        const uint32_t b = 4u * static_cast<uint32_t>(es + off + sub);
-        cc = __builtin_nontemporal_load(reinterpret_cast<const int32_t*>(colp + b));
-        vv = __builtin_nontemporal_load(reinterpret_cast<const float*>(valp + b));
-      }
-    };
-    auto request = [&](int q, int u) {  // stream edge q -> ring buffer u (q wave-uniform)
-#if GNN_SPMM_READLANE
-      const int ce = slot_lane_i<LPR>(c, q & (LPR - 1), LPR, grp);
-      const float we = slot_lane_f<LPR>(v, q & (LPR - 1), LPR, grp);
-#else
-      const int src = grp * LPR + (q & (LPR - 1));
-      const int ce = __shfl(c, src, kWave);
-      const float we = __shfl(v, src, kWave);
-#endif
-      const bool ok = q < ns;
-      w[u] = ok ? we : 0.f;
-      if constexpr (FX::kMixed) {
-        const MixedRow<VW, XT, HT> mr(P.x, P.ldx, P.xh, P.ldh, ce);
-        hubrow[u] = mr.hub;
+  len = wave_uniform(len);
+  flush_upto(es);  // leading rows without edges
+  for (int off = 0; off < len; off += CH) {
+    const int cb = es + off;  // this slot's chunk: lane `sub` holds edges cb + sub + j * LPR
+    int c[CPL];
+    float v[CPL];
 #pragma unroll
-        for (int ch = 0; ch < NCH; ++ch) {
-          const int64_t f = static_cast<int64_t>(ch * LPR + sub) * VW;
-          xv[u][ch] = mr.load(f, ok && f < P.feat);
-        }
-      } else {
-        const XT* xr = masked_row<HUB, XT>(xs, P.ldx, dbase, dld, ce);
-#pragma unroll
-        for (int ch = 0; ch < NCH; ++ch) {
-          const int64_t f = static_cast<int64_t>(ch * LPR + sub) * VW;
-          xv[u][ch] = (ok && f < P.feat) ? FX::RX::load(xr + ch * LPR * VW) : FX::zero();
-        }
+    for (int j = 0; j < CPL; ++j) {
+      c[j] = 0;
+      v[j] = 0.f;
+      if (cb + sub + j * LPR < ee) {
+        c[j] = __builtin_nontemporal_load(P.col + e0 + cb + sub + j * LPR);
+        v[j] = __builtin_nontemporal_load(P.val + e0 + cb + sub + j * LPR);
       }
-    };
-    load_edges(0, c, v);
-    if (kAhead == CH && CH < len) load_edges(CH, cn, vn);
-#pragma unroll
-    for (int u = 0; u < U; ++u) request(u, u);
-    flush_upto(es);  // leading rows without edges
-    for (int p = 0; p < len; p += U) {
-      const int q = p + U;  // the batch requested while the batch at p is consumed
-      if ((q & (CH - 1)) == 0) {  // it opens a chunk (wave-uniform, as every branch here)
-        c = cn;
-        v = vn;
-      }
-      if (((q + kAhead) & (CH - 1)) == 0 && q + kAhead < len) load_edges(q + kAhead, cn, vn);
+    }
+    const int n = min(CH, len - off);  // wave-uniform
+    auto batch = [&](int k, auto kc) {  // edges k .. k + U - 1 of the chunk (kc: k when constant)
+      typename FX::Raw xv[U][NCH];
+      float w[U];
+      bool hubrow[FX::kMixed ? U : 1] = {};
 #pragma unroll
       for (int u = 0; u < U; ++u) {
-        flush_upto(es + p + u);  // rows that end before this edge (all of them past ee)
+        int ce;
+        float we;
+        if constexpr (CPL == 1) {
+          const int src = grp * LPR + ((k + u) & (LPR - 1));
+          ce = __shfl(c[0], src, kWave);
+          we = __shfl(v[0], src, kWave);
+        } else {  // k is a constant here: the register of edge k + u is known
+          constexpr int K0 = decltype(kc)::value;
+          const int src = grp * LPR + ((K0 + u) % LPR);
+          ce = __shfl(c[(K0 + u) / LPR], src, kWave);
+          we = __shfl(v[(K0 + u) / LPR], src, kWave);
+        }
+        const bool ok = cb + k + u < ee;
+        w[u] = ok ? we : 0.f;
+        if constexpr (FX::kMixed) {
+          const MixedRow<VW, XT, HT> mr(P.x, P.ldx, P.xh, P.ldh, ce);
+          hubrow[u] = mr.hub;
+#pragma unroll
+          for (int ch = 0; ch < NCH; ++ch) {
+            const int64_t f = static_cast<int64_t>(ch * LPR + sub) * VW;
+            xv[u][ch] = mr.load(f, ok && f < P.feat);
+          }
+        } else {
+          const XT* xr = masked_row<HUB, XT>(xs, P.ldx, dbase, dld, ce);
+#pragma unroll
+          for (int ch = 0; ch < NCH; ++ch) {
+            const int64_t f = static_cast<int64_t>(ch * LPR + sub) * VW;
+            xv[u][ch] = (ok && f < P.feat) ? FX::RX::load(xr + ch * LPR * VW) : FX::zero();
+          }
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        flush_upto(cb + k + u);  // rows that end before this edge (all of them past ee)
 #pragma unroll
         for (int ch = 0; ch < NCH; ++ch)
           acc[ch] += w[u] * FX::f32(xv[u][ch], hubrow[FX::kMixed ? u : 0]);
-        request(q + u, u);
       }
-    }
-  } else {
-    flush_upto(es);  // leading rows without edges
-    for (int off = 0; off < len; off += CH) {
-      const int cb = es + off;  // this slot's chunk: lane `sub` holds edges cb + sub + j * LPR
-      int c[CPL];
-      float v[CPL];
-#pragma unroll
-      for (int j = 0; j < CPL; ++j) {
-        c[j] = 0;
-        v[j] = 0.f;
-        if (cb + sub + j * LPR < ee) {
-          c[j] = __builtin_nontemporal_load(P.col + e0 + cb + sub + j * LPR);
-          v[j] = __builtin_nontemporal_load(P.val + e0 + cb + sub + j * LPR);
-        }
+    };
+    if constexpr (CPL == 1) {
+      for (int k = 0; k < n; k += U) batch(k, std::integral_constant<int, 0>{});
+    } else {  // CH / U batches, unrolled (the register index of each edge is a constant)
+      static_assert(CH / U <= 4, "at most 4 batches per chunk");
+      batch(0, std::integral_constant<int, 0>{});
+      if constexpr (CH / U > 1) {
+        if (U < n) batch(U, std::integral_constant<int, U>{});
       }
-      const int n = min(CH, len - off);  // wave-uniform
-      auto batch = [&](int k, auto kc) {  // edges k .. k + U - 1 of the chunk (kc: k when constant)
-        typename FX::Raw xv[U][NCH];
-        float w[U];
-        bool hubrow[FX::kMixed ? U : 1] = {};
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          int ce;
-          float we;
-          if constexpr (CPL == 1) {
-#if GNN_SPMM_READLANE
-            ce = slot_lane_i<LPR>(c[0], (k + u) & (LPR - 1), LPR, grp);
-            we = slot_lane_f<LPR>(v[0], (k + u) & (LPR - 1), LPR, grp);
-#else
-            const int src = grp * LPR + ((k + u) & (LPR - 1));
-            ce = __shfl(c[0], src, kWave);
-            we = __shfl(v[0], src, kWave);
-#endif
-          } else {  // k is a constant here: the register of edge k + u is known
-            constexpr int K0 = decltype(kc)::value;
-            const int src = grp * LPR + ((K0 + u) % LPR);
-            ce = __shfl(c[(K0 + u) / LPR], src, kWave);
-            we = __shfl(v[(K0 + u) / LPR], src, kWave);
-          }
-          const bool ok = cb + k + u < ee;
-          w[u] = ok ? we : 0.f;
-          if constexpr (FX::kMixed) {
-            const MixedRow<VW, XT, HT> mr(P.x, P.ldx, P.xh, P.ldh, ce);
-            hubrow[u] = mr.hub;
-#pragma unroll
-            for (int ch = 0; ch < NCH; ++ch) {
-              const int64_t f = static_cast<int64_t>(ch * LPR + sub) * VW;
-              xv[u][ch] = mr.load(f, ok && f < P.feat);
-            }
-          } else if constexpr (kLean) {
-            const XT* xr = masked_row<HUB, XT>(xs, P.ldx, dbase, dld, ce);
-#pragma unroll
-            for (int ch = 0; ch < NCH; ++ch) {
-              const int64_t f = static_cast<int64_t>(ch * LPR + sub) * VW;
-              xv[u][ch] = (ok && f < P.feat) ? FX::RX::load(xr + ch * LPR * VW) : FX::zero();
-            }
-          } else {
-            const XT* xr = (HUB && ce < 0) ? P.xh + static_cast<int64_t>(-1 - ce) * P.ldh
-                                           : P.x + static_cast<int64_t>(ce) * P.ldx;
-#pragma unroll
-            for (int ch = 0; ch < NCH; ++ch) {
-              const int64_t f = static_cast<int64_t>(ch * LPR + sub) * VW;
-              xv[u][ch] = (ok && f < P.feat) ? FX::RX::load(xr + f) : FX::zero();
-            }
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          flush_upto(cb + k + u);  // rows that end before this edge (all of them past ee)
-#pragma unroll
-          for (int ch = 0; ch < NCH; ++ch)
-            acc[ch] += w[u] * FX::f32(xv[u][ch], hubrow[FX::kMixed ? u : 0]);
-        }
-      };
-      if constexpr (CPL == 1) {
-        for (int k = 0; k < n; k += U) batch(k, std::integral_constant<int, 0>{});
-      } else {  // CH / U batches, unrolled (the register index of each edge is a constant)
-        static_assert(CH / U <= 4, "at most 4 batches per chunk");
-        batch(0, std::integral_constant<int, 0>{});
-        if constexpr (CH / U > 1) {
-          if (U < n) batch(U, std::integral_constant<int, U>{});
-        }
-        if constexpr (CH / U > 2) {
-          if (2 * U < n) batch(2 * U, std::integral_constant<int, 2 * U>{});
-        }
-        if constexpr (CH / U > 3) {
-          if (3 * U < n) batch(3 * U, std::integral_constant<int, 3 * U>{});
-        }
+      if constexpr (CH / U > 2) {
+        if (2 * U < n) batch(2 * U, std::integral_constant<int, 2 * U>{});
+      }
+      if constexpr (CH / U > 3) {
+        if (3 * U < n) batch(3 * U, std::integral_constant<int, 3 * U>{});
       }
     }
   }
-  flush_upto(kLean ? kNever - 1 : 0x7fffffff);  // the last row and trailing rows without edges
+  flush_upto(kNever - 1);  // the last row and trailing rows without edges
 }
 
-template <int VW, int LPR, int NCH, int U, bool NT, bool STAGE = false, bool HUB = false,
-          bool TASKS = false, int CPL = 1, typename XT = float, typename HT = XT>
+template <int VW, int LPR, int NCH, int U, bool NT, bool HUB = false, bool TASKS = false,
+          int CPL = 1, typename XT = float, typename HT = XT>
 __global__ __launch_bounds__(kBlock) void spmm_csr_kernel(SpmmParamsT<XT, HT> P) {
   const int lane = threadIdx.x & (kWave - 1);
   const int64_t wave = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + (threadIdx.x >> 6);
-  __shared__ f4 stage_all[STAGE ? kWavesPerBlock * U * kWave : 1];
-  f4* stage = stage_all + (STAGE ? (threadIdx.x >> 6) * U * kWave : 0);
   const int sub = lane & (LPR - 1);
   typename Vec<VW>::T acc[NCH];
 #pragma unroll
@@ -794,11 +579,8 @@ __global__ __launch_bounds__(kBlock) void spmm_csr_kernel(SpmmParamsT<XT, HT> P)
     const int32_t row = P.seg_row[wave];
     const int64_t beg = P.seg_begin[wave];
     const int64_t end = min(beg + P.seg_len, P.rowptr[row + 1]);
-    if constexpr (STAGE)
-      gather_rows_lds<LPR, U>(P.col, P.val, beg, end, P.x, P.ldx, lane, acc[0], stage);
-    else
-      gather_rows<VW, LPR, NCH, U, HUB, XT, HT>(P.col, P.val, beg, end, P.x, P.ldx, P.feat, lane,
-                                                acc, P.xh, P.ldh);
+    gather_rows<VW, LPR, NCH, U, HUB, XT, HT>(P.col, P.val, beg, end, P.x, P.ldx, P.feat, lane,
+                                              acc, P.xh, P.ldh);
     reduce_slots<VW, LPR, NCH>(acc);
     if (lane < LPR) store_slot_row<VW, LPR, NCH, false>(P.partial + wave * P.ldp, nullptr, P.feat,
                                                         0u, sub, acc);
@@ -808,12 +590,8 @@ __global__ __launch_bounds__(kBlock) void spmm_csr_kernel(SpmmParamsT<XT, HT> P)
     const int64_t i = wave - P.seg_waves;
     if (i >= P.n_mid) return;
     const int64_t row = P.mid_row ? P.mid_row[i] : i;
-    if constexpr (STAGE)
-      gather_rows_lds<LPR, U>(P.col, P.val, P.rowptr[row], P.rowptr[row + 1], P.x, P.ldx, lane,
-                              acc[0], stage);
-    else
-      gather_rows<VW, LPR, NCH, U, HUB, XT, HT>(P.col, P.val, P.rowptr[row], P.rowptr[row + 1],
-                                                P.x, P.ldx, P.feat, lane, acc, P.xh, P.ldh);
+    gather_rows<VW, LPR, NCH, U, HUB, XT, HT>(P.col, P.val, P.rowptr[row], P.rowptr[row + 1],
+                                              P.x, P.ldx, P.feat, lane, acc, P.xh, P.ldh);
     reduce_slots<VW, LPR, NCH>(acc);
     if (lane < LPR) store_slot_row<VW, LPR, NCH, NT>(P.y + row * P.ldy, P.bias, P.feat, P.flags,
                                                      sub, acc);
@@ -822,20 +600,10 @@ __global__ __launch_bounds__(kBlock) void spmm_csr_kernel(SpmmParamsT<XT, HT> P)
   if constexpr (TASKS) {  // ---- packed row tasks
     const int64_t t = wave - P.seg_waves - P.mid_waves;
     if (t < P.n_task) packed_rows<VW, LPR, NCH, U, NT, HUB, CPL, XT, HT>(P, t, lane);
-  } else if constexpr (!kSmallSplit) {
-    // ---- packed small rows (unless they have their own launch, spmm_small_kernel)
+  } else {  // ---- packed small rows
     small_rows<VW, LPR, NCH, NT, small_unroll<NCH>(), XT, HT>(P, wave - P.seg_waves - P.mid_waves,
                                                               lane);
   }
-}
-
-// Packed small rows as their own launch: their unrolled loads then do not set the
-// register budget (and so the occupancy) of the segment / mid-row waves.
-template <int VW, int LPR, int NCH, bool NT, typename XT = float, typename HT = XT>
-__global__ __launch_bounds__(kBlock) void spmm_small_kernel(SpmmParamsT<XT, HT> P) {
-  small_rows<VW, LPR, NCH, NT, kSmallSplitUnroll, XT, HT>(
-      P, static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + (threadIdx.x >> 6),
-      threadIdx.x & (kWave - 1));
 }
 
 // y[long_row[i]] = act(sum_{s in segs(i)} partial[s] + bias).
@@ -908,15 +676,14 @@ struct SpmmLaunchT {
 };
 typedef SpmmLaunchT<> SpmmLaunch;
 
-template <int VW, int LPR, int NCH, int U_OVERRIDE = 0, bool NT = true, bool STAGE = false,
-          bool HUB = false, typename XT = float, typename HT = XT>
+template <int VW, int LPR, int NCH, bool HUB = false, typename XT = float, typename HT = XT>
 static int launch_spmm_t(const SpmmLaunchT<XT, HT>& L) {
-  constexpr int U = U_OVERRIDE ? U_OVERRIDE : (NCH >= 4 ? 1 : (NCH == 2 ? 2 : GNN_SPMM_U));
+  constexpr int U = NCH >= 4 ? 1 : (NCH == 2 ? 2 : GNN_SPMM_U);
   constexpr int EPI = kWave / LPR;
   SpmmParamsT<XT, HT> p = L.p;
   const int64_t seg_blocks = (p.n_seg + kWavesPerBlock - 1) / kWavesPerBlock;
   const int64_t mid_blocks = (p.n_mid + kWavesPerBlock - 1) / kWavesPerBlock;
-  if constexpr (VW == Elem<XT>::kVec && !STAGE) {  // the vector path of XT
+  if constexpr (VW == Elem<XT>::kVec) {  // the vector path of XT
     if (p.task_row != nullptr) {  // packed row tasks in place of the small-row class
       // neighbour rows in flight per slot: at most LPR (a batch never straddles a chunk of LPR
       // edges), so the narrow rows (LPR = 2: feat 5-8, 32 slots per wave) take 2
@@ -931,51 +698,43 @@ static int launch_spmm_t(const SpmmLaunchT<XT, HT>& L) {
       const int64_t blocks = seg_blocks + mid_blocks + task_blocks;
       if (blocks > 0x7fffffffLL) return GNN_E_UNSUPPORTED;
       if (blocks > 0)
-        hipLaunchKernelGGL((spmm_csr_kernel<VW, LPR, NCH, UT, NT, false, HUB, true, CPL, XT, HT>),
+        hipLaunchKernelGGL((spmm_csr_kernel<VW, LPR, NCH, UT, true, HUB, true, CPL, XT, HT>),
                            dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, L.stream, p);
       if (L.n_long > 0)
-        hipLaunchKernelGGL((spmm_fixup_kernel<VW, LPR, NCH, NT>), dim3(static_cast<unsigned>(L.n_long)),
+        hipLaunchKernelGGL((spmm_fixup_kernel<VW, LPR, NCH, true>), dim3(static_cast<unsigned>(L.n_long)),
                            dim3(kBlock), 0, L.stream, L.long_row, L.long_seg_ptr, L.n_long, p.partial,
                            p.ldp, p.feat, p.bias, p.y, p.ldy, p.flags & ~GNN_EPI_SKIP_EMPTY);
       return launch_status();
     }
   }
   if (p.task_row != nullptr) return GNN_E_UNSUPPORTED;
-  constexpr int SU = kSmallSplit ? kSmallSplitUnroll : small_unroll<NCH>();
+  constexpr int SU = small_unroll<NCH>();
   const int64_t small_waves = (p.n_small + EPI * SU - 1) / (EPI * SU);
   const int64_t small_blocks = (small_waves + kWavesPerBlock - 1) / kWavesPerBlock;
   p.seg_waves = seg_blocks * kWavesPerBlock;
   p.mid_waves = mid_blocks * kWavesPerBlock;
-  const int64_t blocks = seg_blocks + mid_blocks + (kSmallSplit ? 0 : small_blocks);
-  if (blocks > 0x7fffffffLL || small_blocks > 0x7fffffffLL) return GNN_E_UNSUPPORTED;
+  const int64_t blocks = seg_blocks + mid_blocks + small_blocks;
+  if (blocks > 0x7fffffffLL) return GNN_E_UNSUPPORTED;
   if (blocks > 0) {
-    hipLaunchKernelGGL((spmm_csr_kernel<VW, LPR, NCH, U, NT, STAGE, HUB, false, 1, XT, HT>),
-                       dim3(static_cast<unsigned>(blocks)), dim3(kBlock), GNN_SPMM_LDS_PAD,
-                       L.stream, p);
-  }
-  if constexpr (kSmallSplit) {  // (not instantiated otherwise: its 16 unrolled loads spill)
-    if (small_blocks > 0)
-      hipLaunchKernelGGL((spmm_small_kernel<VW, LPR, NCH, NT, XT, HT>),
-                         dim3(static_cast<unsigned>(small_blocks)), dim3(kBlock), 0, L.stream, p);
+    hipLaunchKernelGGL((spmm_csr_kernel<VW, LPR, NCH, U, true, HUB, false, 1, XT, HT>),
+                       dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, L.stream, p);
   }
   if (L.n_long > 0) {
-    hipLaunchKernelGGL((spmm_fixup_kernel<VW, LPR, NCH, NT>), dim3(static_cast<unsigned>(L.n_long)),
+    hipLaunchKernelGGL((spmm_fixup_kernel<VW, LPR, NCH, true>), dim3(static_cast<unsigned>(L.n_long)),
                        dim3(kBlock), 0, L.stream, L.long_row, L.long_seg_ptr, L.n_long, p.partial,
                        p.ldp, p.feat, p.bias, p.y, p.ldy, p.flags);
   }
   return launch_status();
 }
 
-template <int VW, int LPR, int NCH, int U_OVERRIDE = 0, bool NT = true, bool STAGE = false,
-          typename XT = float, typename HT = XT>
+template <int VW, int LPR, int NCH, typename XT = float, typename HT = XT>
 static int launch_spmm(const SpmmLaunchT<XT, HT>& L) {
   // two element types: only the hub form exists (spmm_entry never gets here without xh)
   if constexpr (!std::is_same<XT, HT>::value)
-    return L.p.xh ? launch_spmm_t<VW, LPR, NCH, U_OVERRIDE, NT, STAGE, true, XT, HT>(L)
-                  : GNN_E_ARG;
+    return L.p.xh ? launch_spmm_t<VW, LPR, NCH, true, XT, HT>(L) : GNN_E_ARG;
   else
-    return L.p.xh ? launch_spmm_t<VW, LPR, NCH, U_OVERRIDE, NT, STAGE, true, XT, HT>(L)
-                  : launch_spmm_t<VW, LPR, NCH, U_OVERRIDE, NT, STAGE, false, XT, HT>(L);
+    return L.p.xh ? launch_spmm_t<VW, LPR, NCH, true, XT, HT>(L)
+                  : launch_spmm_t<VW, LPR, NCH, false, XT, HT>(L);
 }
 
 // Picks (VW, LPR, NCH) for one column block of width feat (<= 64 * max_nch(VW) * VW).
@@ -984,19 +743,19 @@ static int dispatch_spmm(const SpmmLaunchT<XT, HT>& L) {
   const int64_t nv = (L.p.feat + VW - 1) / VW;  // vectors per row
   if (nv <= 64) {
     switch (next_pow2_le64(nv)) {
-      case 1: return launch_spmm<VW, 1, 1, 0, true, false, XT, HT>(L);
-      case 2: return launch_spmm<VW, 2, 1, 0, true, false, XT, HT>(L);
-      case 4: return launch_spmm<VW, 4, 1, 0, true, false, XT, HT>(L);
-      case 8: return launch_spmm<VW, 8, 1, 0, true, false, XT, HT>(L);
-      case 16: return launch_spmm<VW, 16, 1, 0, true, false, XT, HT>(L);
-      case 32: return launch_spmm<VW, 32, 1, 0, true, false, XT, HT>(L);
-      default: return launch_spmm<VW, 64, 1, 0, true, false, XT, HT>(L);
+      case 1: return launch_spmm<VW, 1, 1, XT, HT>(L);
+      case 2: return launch_spmm<VW, 2, 1, XT, HT>(L);
+      case 4: return launch_spmm<VW, 4, 1, XT, HT>(L);
+      case 8: return launch_spmm<VW, 8, 1, XT, HT>(L);
+      case 16: return launch_spmm<VW, 16, 1, XT, HT>(L);
+      case 32: return launch_spmm<VW, 32, 1, XT, HT>(L);
+      default: return launch_spmm<VW, 64, 1, XT, HT>(L);
     }
   }
-  if (nv <= 128) return launch_spmm<VW, 64, 2, 0, true, false, XT, HT>(L);
-  if (nv <= 256) return launch_spmm<VW, 64, 4, 0, true, false, XT, HT>(L);
+  if (nv <= 128) return launch_spmm<VW, 64, 2, XT, HT>(L);
+  if (nv <= 256) return launch_spmm<VW, 64, 4, XT, HT>(L);
   if constexpr (max_nch(VW) >= 8)
-    return launch_spmm<VW, 64, 8, 0, true, false, XT, HT>(L);
+    return launch_spmm<VW, 64, 8, XT, HT>(L);
   else
     return GNN_E_UNSUPPORTED;  // run_spmm cuts narrower column blocks
 }
@@ -1044,31 +803,10 @@ static bool spmm_vector_ok(const SpmmLaunchT<XT, HT>& L, const XT* x, const floa
 
 template <typename XT, typename HT>
 static int run_spmm(SpmmLaunchT<XT, HT> L, const XT* x, const float* bias, float* y,
-                    float* partial, int64_t feat, int variant) {
+                    float* partial, int64_t feat) {
   constexpr int VX = Elem<XT>::kVec;
   const HT* xh = L.p.xh;
   const bool vec4 = spmm_vector_ok(L, x, bias, y, partial, feat);
-  if (variant >= 0) {  // developer A/B (feat == 128, fp32 vector path only)
-    if constexpr (!std::is_same<XT, float>::value || !std::is_same<HT, float>::value) {
-      return GNN_E_UNSUPPORTED;
-    } else {
-      if (feat != 128 || !vec4) return GNN_E_UNSUPPORTED;
-      L.p.feat = feat;
-      L.p.x = x;
-      L.p.y = y;
-      L.p.bias = bias;
-      L.p.partial = partial;
-      switch (variant) {
-        case 0: return launch_spmm<4, 32, 1, 4, true>(L);  // the shipped configuration
-        case 1: return launch_spmm<4, 32, 1, 8, true>(L);
-        case 2: return launch_spmm<4, 32, 1, 2, true>(L);
-        case 3: return launch_spmm<4, 32, 1, 4, true, true>(L);   // LDS-DMA staged gather
-        case 4: return launch_spmm<4, 32, 1, 8, true, true>(L);   // LDS-DMA, 8 slots in flight
-        case 7: return launch_spmm<4, 32, 1, 4, false>(L);
-        default: return GNN_E_ARG;
-      }
-    }
-  }
   const int64_t vw = vec4 ? VX : 1;
   const int64_t blk = 64 * max_nch(vw) * vw;  // widest column block one launch covers
   for (int64_t c0 = 0; c0 < feat; c0 += blk) {
@@ -1092,7 +830,7 @@ static int spmm_entry(const int64_t* rowptr, const int32_t* col, const float* va
                       const int32_t* long_seg_ptr, int64_t n_long, const int32_t* small_row,
                       const int32_t* small_col, const float* small_val, int64_t n_small,
                       const int32_t* mid_row, int64_t n_mid, float* partial, uint32_t flags,
-                      void* stream, int variant, const HT* xh = nullptr, int64_t ldh = 0,
+                      void* stream, const HT* xh = nullptr, int64_t ldh = 0,
                       const int32_t* task_row = nullptr, int64_t n_task = 0) {
   int rc = check_spmm_args(rowptr, n_rows, x, ldx, feat, y, ldy, seg_len, n_seg, n_long, n_small,
                            n_mid, seg_row, seg_begin, long_row, long_seg_ptr, small_row, small_col,
@@ -1129,7 +867,7 @@ static int spmm_entry(const int64_t* rowptr, const int32_t* col, const float* va
   L.long_seg_ptr = long_seg_ptr;
   L.n_long = plan ? n_long : 0;
   L.stream = static_cast<hipStream_t>(stream);
-  return run_spmm(L, x, bias, y, partial, feat, variant);
+  return run_spmm(L, x, bias, y, partial, feat);
 }
 
 }  // namespace gnn

@@ -69,18 +69,6 @@ static float* y_shifted(float* y, int c, const TfEpi& epi) {
 }
 // split3 / swz6 / x6_pitch (fp32 products from bf16 MFMAs): common.hpp
 
-#ifndef GNN_TF_SINGLE_BUFFER
-#define GNN_TF_SINGLE_BUFFER 0  // A/B: the round-2 one-buffer tile loop (two barriers per tile)
-#endif
-#ifndef GNN_TF_X6_PIPE
-#define GNN_TF_X6_PIPE 0  // A/B: X6 fragments of k-step s + 1 read during step s's MFMAs
-#endif
-#ifndef GNN_TF_K256_CB2
-#define GNN_TF_K256_CB2 0  // A/B: K = 256 -> 128 as 4 waves x 2 column blocks
-#endif
-#ifndef GNN_TF_ONE256
-#define GNN_TF_ONE256 1  // 0 = A/B: 256 output columns at K >= 128 as two 128-column launches
-#endif
 #ifndef GNN_TF_PREFETCH
 #define GNN_TF_PREFETCH 1  // X tiles in flight in registers ahead of the one being multiplied
 #endif
@@ -126,13 +114,12 @@ __global__ __launch_bounds__(NW * kWave) void gcn_transform_kernel(
   constexpr int LDA = 4 * TileLds<K>::L4;  // LDS row pitch (floats)
   constexpr int V4 = TR * K / 4;       // float4s per tile
   constexpr int NV = (V4 + kTfBlock - 1) / kTfBlock;  // per thread
-  constexpr int NBUF = GNN_TF_SINGLE_BUFFER ? 1 : 2;
   static_assert(S % XC == 0 && XC % 4 == 0, "X chunks of whole float4s");
   constexpr int S32 = K / 32;  // X6: bf16 MFMA k-steps (32 k each, 8 per lane quarter)
   constexpr int P6 = x6_pitch<K>();
   constexpr int PLANE = TR * P6;  // bytes per bf16 plane
   static_assert(!X6 || (K >= 64 && K % 64 == 0), "X6 tiles: K in {64, 128, 256}");
-  __shared__ float xt[NBUF][X6 ? 3 * PLANE / 4 : TR * LDA];
+  __shared__ float xt[2][X6 ? 3 * PLANE / 4 : TR * LDA];
   __shared__ float part[CLS ? 2 : 1][CLS ? NW * TR * kMaxCls : 1];  // per-wave logit partials
   const int lane = threadIdx.x & (kWave - 1);
   const int wv = threadIdx.x >> 6;
@@ -182,7 +169,7 @@ __global__ __launch_bounds__(NW * kWave) void gcn_transform_kernel(
   // PF tiles in flight in registers: tile it + PF is requested while tile it is multiplied
   // (slot it % PF; the loop is unrolled by PF so every slot index is a constant)
   constexpr int PF = GNN_TF_PREFETCH;
-  static_assert(PF >= 1 && PF <= 4 && (PF == 1 || NBUF == 2), "prefetch depth 1..4");
+  static_assert(PF >= 1 && PF <= 4, "prefetch depth 1..4");
   float4 pre[PF][NV];
   // Tile loads through a buffer descriptor of the tile's rows: the hardware range check
   // returns 0 for rows past the end (and for a tile past the last), so the loads need no
@@ -233,21 +220,15 @@ __global__ __launch_bounds__(NW * kWave) void gcn_transform_kernel(
     }
   };
   fetch(pre[0], blockIdx.x);
-  if (NBUF == 2) {
-    stage(xt[0], pre[0]);
-    __syncthreads();
-  }
+  stage(xt[0], pre[0]);
+  __syncthreads();
 #pragma unroll
   for (int f = 1; f < PF; ++f) fetch(pre[f], blockIdx.x + static_cast<int64_t>(f) * gridDim.x);
   int it = 0;
   auto body = [&](auto slot, int64_t g) {  // one tile; uniform over the block
     constexpr int SL = decltype(slot)::value;  // this tile's register slot (already staged)
     constexpr int SN = (SL + 1) % PF;          // the next tile's
-    const float* cur = xt[NBUF == 2 ? (it & 1) : 0];
-    if (NBUF == 1) {
-      stage(xt[0], pre[0]);
-      __syncthreads();
-    }
+    const float* cur = xt[it & 1];
     const int64_t row0 = g * TR;
     // output rows of this lane's rows, requested first: the epilogue's wait for them then does
     // not also wait for the prefetch issued after them (the counter retires in order)
@@ -271,28 +252,12 @@ __global__ __launch_bounds__(NW * kWave) void gcn_transform_kernel(
         for (int cb = 0; cb < CB; ++cb) acc[j][cb] = tf32x4{0.f, 0.f, 0.f, 0.f};
         const int rr = j * 16 + r;
         const char* xr = reinterpret_cast<const char*>(cur) + rr * P6;
-#if GNN_TF_X6_PIPE
-        // the next k-step's three fragments are read while this step's MFMAs run
-        bf16x8 fr[2][3];
-        auto rd = [&](int s6, bf16x8 (&f)[3]) {
-          const char* xp = xr + 16 * ((q * S32 + s6) ^ swz6<K>(rr));
-          f[0] = *reinterpret_cast<const bf16x8*>(xp);
-          f[1] = *reinterpret_cast<const bf16x8*>(xp + PLANE);
-          f[2] = *reinterpret_cast<const bf16x8*>(xp + 2 * PLANE);
-        };
-        rd(0, fr[0]);
-#endif
 #pragma unroll
         for (int s6 = 0; s6 < S32; ++s6) {
-#if GNN_TF_X6_PIPE
-          if (s6 + 1 < S32) rd(s6 + 1, fr[(s6 + 1) & 1]);
-          const bf16x8 x0 = fr[s6 & 1][0], x1 = fr[s6 & 1][1], x2 = fr[s6 & 1][2];
-#else
           const char* xp = xr + 16 * ((q * S32 + s6) ^ swz6<K>(rr));
           const bf16x8 x0 = *reinterpret_cast<const bf16x8*>(xp);
           const bf16x8 x1 = *reinterpret_cast<const bf16x8*>(xp + PLANE);
           const bf16x8 x2 = *reinterpret_cast<const bf16x8*>(xp + 2 * PLANE);
-#endif
 #pragma unroll
           for (int cb = 0; cb < CB; ++cb) {  // smallest terms first
             tf32x4 a = acc[j][cb];
@@ -344,7 +309,7 @@ __global__ __launch_bounds__(NW * kWave) void gcn_transform_kernel(
     // the next tile goes to the other buffer while the last MFMAs drain (nobody reads it:
     // the barrier that ended the previous tile saw every wave's reads of it complete)
     __builtin_amdgcn_sched_barrier(0);  // ... and the staging (which waits for them) after the MFMAs
-    if (NBUF == 2) stage(xt[(it + 1) & 1], pre[SN]);
+    stage(xt[(it + 1) & 1], pre[SN]);
 #pragma unroll
     for (int j = 0; j < TR / 16; ++j) {
       // acc[j][cb][i] = Y[row0 + 16 j + r][(wv*CB + cb)*16 + 4q + i]
@@ -527,13 +492,6 @@ template <int K, int CB, int NW, bool RELU>
 static int launch_transform(const float* x, int64_t ldx, int64_t n_rows, const float* w,
                             float* y, int64_t ldy, const RowIdx& ri, const Classifier& cls, const TfEpi& epi, hipStream_t s) {
   constexpr int64_t slots = GNN_TF_GRID * kTfWaves / NW;
-#ifdef GNN_TF_TR32_ROWS  // A/B: 16-row tiles below GNN_TF_TR16_ROWS, 32-row below this
-#ifndef GNN_TF_TR16_ROWS
-#define GNN_TF_TR16_ROWS (32 * 2 * slots)
-#endif
-  if (n_rows < GNN_TF_TR16_ROWS) return launch_transform_tr<K, CB, NW, RELU, 16>(x, ldx, n_rows, w, y, ldy, ri, cls, epi, s);
-  if (n_rows < GNN_TF_TR32_ROWS) return launch_transform_tr<K, CB, NW, RELU, 32>(x, ldx, n_rows, w, y, ldy, ri, cls, epi, s);
-#endif
   // X6 at K = 256: 16-row tiles at every size (in one process, tools/transform_x6_ab.py,
   // profiles/r03x_transform_x6_ab.log: 62K / 200K x 256 -> 128 30.9 / 79.9 vs 32.9 / 89.7 us
   // with 32-row tiles; K = 128 keeps 32: 1M x 128 -> 128 205 vs 211 us)
@@ -553,7 +511,7 @@ static int dispatch_transform(int64_t fout, const float* x, int64_t ldx, int64_t
                               const Classifier& cls, const TfEpi& epi, hipStream_t s) {
   if (fout == 64) return launch_transform<K, 1, kTfWaves, RELU>(x, ldx, n_rows, w, y, ldy, ri, cls, epi, s);
   if (fout == 128) {
-    if constexpr (K <= 128 || GNN_TF_K256_CB2)
+    if constexpr (K <= 128)
       return launch_transform<K, 2, kTfWaves, RELU>(x, ldx, n_rows, w, y, ldy, ri, cls, epi, s);
     else
       return launch_transform<K, 1, 8, RELU>(x, ldx, n_rows, w, y, ldy, ri, cls, epi, s);
@@ -568,19 +526,12 @@ static int dispatch_transform(int64_t fout, const float* x, int64_t ldx, int64_t
       if (rc != GNN_OK) return rc;
       return dispatch_transform<K, RELU>(128, x, ldx, n_rows, w + 128 * K, y_shifted(y, 128, epi),
                                         ldy, ri, cls, epi.shifted(128), s);
-    } else if constexpr (GNN_TF_ONE256) {
+    } else {
       // one launch, 8 waves x 2 column blocks (128 W values per lane resident, 200 VGPRs):
       // X read and staged once for all 256 columns. In one process (tools/transform_tile_ab.py,
       // profiles/r03o_transform_one256_ab.log): 10M x 256 -> 256 9.63 ms (136 TF/s) vs 10.57
       // as two launches vs 9.95 hipBLASLt; 1M x 128 -> 256 0.545 vs 0.618 vs 0.628 ms
       return launch_transform<K, 2, 8, RELU>(x, ldx, n_rows, w, y, ldy, ri, cls, epi, s);
-    } else {
-      // A/B: two launches of the 128-column kernel, one per half of W's rows (X read twice)
-      if (cls.logits != nullptr) return GNN_E_UNSUPPORTED;
-      const int rc = dispatch_transform<K, RELU>(128, x, ldx, n_rows, w, y, ldy, ri, cls, epi, s);
-      if (rc != GNN_OK) return rc;
-      return dispatch_transform<K, RELU>(128, x, ldx, n_rows, w + 128 * K, y_shifted(y, 128, epi),
-                                        ldy, ri, cls, epi.shifted(128), s);
     }
   }
   return GNN_E_UNSUPPORTED;

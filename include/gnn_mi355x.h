@@ -1306,20 +1306,6 @@ int gnn_bce_logits_f32(const float* z, int64_t ldz, const void* y, int64_t ldy, 
                        int64_t rows, int64_t cols, float* loss, float* g, int64_t ldg, void* ws,
                        int64_t ws_bytes, void* stream);
 
-/* ---- developer entry (not part of the drop-in surface) ----
- * gnn_dev_spmm_variant_f32: gnn_spmm_csr_f32 at feat == 128 with a compile-time
- * kernel variant (0 shipped: U=4, non-temporal Y stores; 1 U=8; 2 U=2; 3 U=4 and 4 U=8
- * with the neighbour rows staged through LDS by LDS-DMA; 7 U=4 with plain Y stores) and
- * no epilogue, for interleaved A/B timing (tools/spmm_ab.py). */
-int gnn_dev_spmm_variant_f32(const int64_t* rowptr, const int32_t* col, const float* val,
-                             int64_t n_rows, const float* x, int64_t ldx, int64_t feat,
-                             const float* bias, float* y, int64_t ldy, int64_t seg_len,
-                             const int32_t* seg_row, const int64_t* seg_begin, int64_t n_seg,
-                             const int32_t* long_row, const int32_t* long_seg_ptr, int64_t n_long,
-                             const int32_t* small_row, const int32_t* small_col,
-                             const float* small_val, int64_t n_small, const int32_t* mid_row,
-                             int64_t n_mid, float* partial, int32_t variant, void* stream);
-
 /*
  * Edge-cut halo exchange (SURVEY 8(b) gnn_halo_alltoallv; the all-to-all-v that
  * distributed.EdgeCutSpmm / EdgeCutGat run through torch.distributed on the nccl = RCCL

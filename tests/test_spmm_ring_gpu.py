@@ -1,8 +1,9 @@
 """Packed SpMM tasks (spmm_kernels.hpp packed_rows) at the boundaries of a slot's edge stream.
 
-A slot streams its rows' edges through a rolling window of U neighbour rows that stays full
-across batch, (col, val) chunk and row ends, so the shapes here put row ends, chunk ends, runs
-of edgeless rows and the ends of the slots' streams at every offset of that window: against the
+A slot streams its rows' edges in (col, val) chunks of LPR edges and, within a chunk, in batches
+of U neighbour rows: a batch is requested, waited for and summed, and a row is written as soon
+as the stream passes its end. So the shapes here put row ends, chunk ends, runs of edgeless rows
+and the ends of the slots' streams at every offset of a batch and of a chunk: against the
 C oracle (tolerance of tests/test_spmm_gpu.py), and bitwise where the kernel's contract is
 bitwise -- a packed row's sum runs in edge order in one slot, so it does not depend on how the
 rows are cut into tasks, nor on the run.
@@ -168,8 +169,8 @@ def test_hub_ids_xcd_direct(dev, bf16, monkeypatch):
 
 @pytest.mark.parametrize("bad", [float("nan"), float("inf")])
 def test_nonfinite_row_stays_in_its_row(dev, bad, monkeypatch):
-    """One NaN / Inf row of X gathered as the LAST edge of a row -- at every position of the
-    window, just before the row end -- makes that output row non-finite and no other."""
+    """One NaN / Inf row of X gathered as the LAST edge of a row -- at every position of a
+    batch, just before the row end -- makes that output row non-finite and no other."""
     from graphneuralnetwork_amd import ops
     F, n = 128, 600
     rng = np.random.default_rng(3)

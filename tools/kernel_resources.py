@@ -2,11 +2,11 @@
 -Rpass-analysis=kernel-resource-usage (device side only, no GPU needed) and prints VGPRs,
 SGPRs, scratch and occupancy of every instantiated spmm_csr_kernel / spmm_fixup_kernel.
 
-    python tools/kernel_resources.py [-D GNN_SPMM_RING=0 ...] [--all] [--out FILE]
+    python tools/kernel_resources.py [-D GNN_SPMM_TASK_U=8 ...] [--all] [--out FILE]
 
-The template arguments of spmm_csr_kernel are <VW, LPR, NCH, U, NT, STAGE, HUB, TASKS, CPL,
-XT, HT>; the flagship pass 2 (fp32, F = 128, packed tasks over hub ids) is
-<4, 32, 1, 4, true, false, true, true, 1, float, float>.
+The template arguments of spmm_csr_kernel are <VW, LPR, NCH, U, NT, HUB, TASKS, CPL, XT, HT>;
+the flagship pass 2 (fp32, F = 128, packed tasks over hub ids) is
+<4, 32, 1, 4, true, true, true, 1, float, float>.
 """
 import argparse
 import re

@@ -28,6 +28,14 @@ sys.path.insert(0, str(ROOT))
 # not kept: the one-wave-per-row mid path already overlaps those rows' latency.
 # GCN transform grid (tools/transform_ab.py --variants, profiles/r02m_transform_ab.log):
 # 512 workgroups 0.300 ms at 1M x 128 x 128, 256: 0.333, 768: 0.316, 1024: 0.30x.
+# Retired with their code (DESIGN.md section 6 keeps the rows, git history the arms):
+# small rows in their own launch (split*, sp*u8); occupancy caps by dynamic LDS (wg6 .. wg2);
+# edge (col, val) moved to the edge slots by v_readlane + select instead of ds_bpermute:
+# slower (cfg2 0.946 vs 0.870 ms, ns 11.87 vs 11.79 ms, profiles/r05u_readlane_*.log);
+# the schedule of a packed task, cfg2 --ordered --bias,
+# profiles/r07_lib_ab_*.log: bias in registers -2.3 .. -3.1 %, with the lean bookkeeping
+# -3.0 .. -3.3 % (both kept, now the only form); the ring +5 .. +9 % (slower), 2 % less slow
+# with the next chunk prefetched (parent, parent2, breg, lean, ring, ringpf).
 VARIANTS = {
     "base": [],
     "tu2": ["GNN_SPMM_TASK_U=2"],
@@ -41,14 +49,6 @@ VARIANTS = {
     "small2": ["GNN_SPMM_SMALL_UNROLL=2"],
     "small8": ["GNN_SPMM_SMALL_UNROLL=8"],
     "small16": ["GNN_SPMM_SMALL_UNROLL=16"],
-    "split8": ["GNN_SPMM_SMALL_SPLIT=1", "GNN_SPMM_SMALL_SPLIT_UNROLL=8"],
-    "split16": ["GNN_SPMM_SMALL_SPLIT=1", "GNN_SPMM_SMALL_SPLIT_UNROLL=16"],
-    "split32": ["GNN_SPMM_SMALL_SPLIT=1", "GNN_SPMM_SMALL_SPLIT_UNROLL=32"],
-    # occupancy caps by dynamic LDS (160 KiB per CU): at most 6 / 4 / 3 / 2 workgroups per CU
-    "wg6": ["GNN_SPMM_LDS_PAD=26624", "GNN_GAT_LDS_PAD=26624", "GNN_SAGE_LDS_PAD=26624"],
-    "wg4": ["GNN_SPMM_LDS_PAD=40960", "GNN_GAT_LDS_PAD=40960", "GNN_SAGE_LDS_PAD=40960"],
-    "wg3": ["GNN_SPMM_LDS_PAD=53248", "GNN_GAT_LDS_PAD=53248", "GNN_SAGE_LDS_PAD=53248"],
-    "wg2": ["GNN_SPMM_LDS_PAD=65536", "GNN_GAT_LDS_PAD=65536", "GNN_SAGE_LDS_PAD=65536"],
     "s16u8": ["GNN_SPMM_SMALL_UNROLL=16", "GNN_SPMM_U=8"],
     "s16u2": ["GNN_SPMM_SMALL_UNROLL=16", "GNN_SPMM_U=2"],
     "small32": ["GNN_SPMM_SMALL_UNROLL=32"],
@@ -59,9 +59,6 @@ VARIANTS = {
     "s4u6": ["GNN_SPMM_SMALL_UNROLL=4", "GNN_SPMM_U=6"],
     "s4u12": ["GNN_SPMM_SMALL_UNROLL=4", "GNN_SPMM_U=12"],
     "s4u16": ["GNN_SPMM_SMALL_UNROLL=4", "GNN_SPMM_U=16"],
-    "sp4u8": ["GNN_SPMM_SMALL_SPLIT=1", "GNN_SPMM_SMALL_SPLIT_UNROLL=4", "GNN_SPMM_U=8"],
-    "sp8u8": ["GNN_SPMM_SMALL_SPLIT=1", "GNN_SPMM_SMALL_SPLIT_UNROLL=8", "GNN_SPMM_U=8"],
-    "sp16u8": ["GNN_SPMM_SMALL_SPLIT=1", "GNN_SPMM_SMALL_SPLIT_UNROLL=16", "GNN_SPMM_U=8"],
     "su2": ["GNN_SAGE_U=2"],
     "su8": ["GNN_SAGE_U=8"],
     "su16": ["GNN_SAGE_U=16"],
@@ -70,20 +67,6 @@ VARIANTS = {
     "sbu4": ["GNN_SAGE_BF16_U=4"],
     "sbu8": ["GNN_SAGE_BF16_U=8"],
     "sbu16": ["GNN_SAGE_BF16_U=16"],
-    # edge (col, val) moved to the edge slots by v_readlane + select instead of ds_bpermute:
-    # slower (cfg2 0.946 vs 0.870 ms, ns 11.87 vs 11.79 ms, profiles/r05u_readlane_*.log)
-    "readlane": ["GNN_SPMM_READLANE=1"],
-    # the schedule of a packed task (spmm_kernels.hpp). "parent" pins every
-    # knob to the schedule before them, whatever the defaults are; "parent2" is the same build
-    # again, for the A/A spread. cfg2 (--ordered --bias), profiles/r07_lib_ab_*.log: bias in
-    # registers -2.3 .. -3.1 %, with the lean bookkeeping -3.0 .. -3.3 % (the default); the ring
-    # +5 .. +9 % (slower), 2 % less slow with the next chunk prefetched: both off.
-    "parent": ["GNN_SPMM_BIAS_REG=0", "GNN_SPMM_LEAN=0", "GNN_SPMM_RING=0", "GNN_SPMM_PREFETCH=0"],
-    "parent2": ["GNN_SPMM_BIAS_REG=0", "GNN_SPMM_LEAN=0", "GNN_SPMM_RING=0", "GNN_SPMM_PREFETCH=0"],
-    "breg": ["GNN_SPMM_BIAS_REG=1", "GNN_SPMM_LEAN=0", "GNN_SPMM_RING=0", "GNN_SPMM_PREFETCH=0"],
-    "lean": ["GNN_SPMM_BIAS_REG=1", "GNN_SPMM_LEAN=1", "GNN_SPMM_RING=0", "GNN_SPMM_PREFETCH=0"],
-    "ring": ["GNN_SPMM_BIAS_REG=1", "GNN_SPMM_LEAN=1", "GNN_SPMM_RING=1", "GNN_SPMM_PREFETCH=0"],
-    "ringpf": ["GNN_SPMM_BIAS_REG=1", "GNN_SPMM_LEAN=1", "GNN_SPMM_RING=1", "GNN_SPMM_PREFETCH=1"],
 }
 
 
