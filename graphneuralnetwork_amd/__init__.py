@@ -8,6 +8,8 @@ state_dict keys as the reference):
 * ``graphneuralnetwork_amd.gat``       -- GraphAttentionLayer, SpGraphAttentionLayer,
                                           GAT, SpGAT                       (GAT/models/*.py)
 * ``graphneuralnetwork_amd.graphsage`` -- SageLayer, GraphSAGE, Aggregator (GraphSAGE/*.py)
+* ``graphneuralnetwork_amd.loss``      -- supervised_loss, accuracy: the loss / accuracy /
+                                          backward lines of the train_eval.py loops
 
 The aggregation hot paths run as hand-written gfx950 HIP kernels in
 ``lib/libgnn_mi355x.so`` behind the C-ABI of ``include/gnn_mi355x.h``.

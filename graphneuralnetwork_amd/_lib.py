@@ -154,6 +154,15 @@ SIGNATURES: dict[str, tuple] = {
     "gnn_bce_logits_workspace_bytes": (_i64, [_i64]),
     "gnn_bce_logits_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64, _i32, _i64, _i64, _vp, _vp, _i64,
                                           _vp, _i64, _vp]),
+    # the head of the supervised steps (sup_head.hip)
+    "gnn_sup_head_supported": (ctypes.c_int, [_i64]),
+    "gnn_sup_head_workspace_bytes": (_i64, [_i64]),
+    "gnn_sup_head_count_index": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _vp]),
+    "gnn_sup_head_count_mask": (ctypes.c_int, [_vp, _i64, _vp, _vp]),
+    "gnn_sup_head_fwd_f32": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i64,
+                                            _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "gnn_sup_head_bwd_f32": (ctypes.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _vp,
+                                            _vp, _vp, _i64, _vp]),
     "gnn_halo_alltoallv_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
     "gnn_halo_rccl_path": (ctypes.c_int, [ctypes.c_char_p, _i64]),
     "gnn_spmm_plan_scratch_bytes": (_i64, [_i64]),

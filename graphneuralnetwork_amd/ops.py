@@ -2266,6 +2266,149 @@ def bce_logits(z: torch.Tensor, y: torch.Tensor, want_grad: bool = True):
     return loss.reshape(()), g
 
 
+# ---------------------------------------------------------------- the supervised head
+IGNORE_INDEX = -100  # nn.CrossEntropyLoss()'s
+
+
+def _sup_head_operands(z: torch.Tensor, labels: torch.Tensor) -> bool:
+    """The shape check of the supervised head's ops (z 2-D, labels given per row), then whether
+    the kernels take the layout: fp32 logits with 2 <= C <= 64 and unit stride along C, int64
+    labels [N]. Float labels (class probabilities) and everything else are torch's."""
+    if z.dim() != 2:
+        raise ValueError(f"logits must be [N, C] (got {tuple(z.shape)})")
+    if labels.dim() < 1 or labels.shape[0] != z.shape[0]:
+        raise ValueError(f"labels must have one entry per row of the logits "
+                         f"(got {tuple(labels.shape)} for {tuple(z.shape)})")
+    N, C = z.shape
+    return bool(z.dtype == torch.float32 and labels.dtype == torch.int64 and labels.dim() == 1
+                and _lib.load().gnn_sup_head_supported(C) and z.stride(1) == 1
+                and (N <= 1 or z.stride(0) >= C))
+
+
+def _new_status(dev) -> torch.Tensor:
+    return torch.zeros(1, dtype=torch.int32, device=dev)
+
+
+def sup_head_count(index: torch.Tensor, N: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """The multiplicity of every row in a selection (gnn_sup_head_count_index / _mask):
+    (count int32 [N], status int32 [1]). ``index``: int64 [n], entries in [-N, 0) wrapping as
+    torch's indexing does, duplicates counted; or a bool mask [N] (converted on the device, no
+    ``nonzero``). An entry outside [-N, N) addresses nothing and sets bit 0 of ``status``."""
+    _require_device(index)
+    if index.dtype not in (torch.int64, torch.bool):
+        raise TypeError(f"index must be int64 or a bool mask (got {index.dtype})")
+    if index.dim() != 1 or (index.dtype == torch.bool and index.shape[0] != N):
+        raise ValueError(f"index must be int64 [n] or bool [{N}] (got {tuple(index.shape)})")
+    lib = _lib.load()
+    dev = index.device
+    index = index.contiguous()
+    count = torch.empty(N, dtype=torch.int32, device=dev)
+    status = _new_status(dev)
+    if index.dtype == torch.bool:
+        _lib.check(lib.gnn_sup_head_count_mask(index.data_ptr(), N, count.data_ptr(),
+                                               _lib.stream_handle(dev)),
+                   "gnn_sup_head_count_mask")
+    else:
+        _lib.check(lib.gnn_sup_head_count_index(
+            index.data_ptr(), index.shape[0], N, count.data_ptr(), status.data_ptr(),
+            _lib.stream_handle(dev)), "gnn_sup_head_count_index")
+    return count, status
+
+
+def sup_head_forward(z: torch.Tensor, labels: torch.Tensor, index: torch.Tensor | None = None,
+                     count: torch.Tensor | None = None, status: torch.Tensor | None = None,
+                     want_correct: bool = True):
+    """``F.cross_entropy(z[index], labels[index])`` (mean, ignore_index -100) and the count of
+    correct predictions ``(argmax(z[index], 1) == labels[index]).sum()`` in one pass and a
+    one-wavefront finish (gnn_sup_head_fwd_f32): (loss 0-dim float32, n_correct 0-dim int64 or
+    None, inv_valid float64 [1] = 1 / the number of rows that are not ignored, status int32 [1]).
+    The selection is ``index`` (int64 [n], duplicates and negative entries as torch's), or
+    ``count`` (int32 [N] from ``sup_head_count``, for a mask), or every row. Rows evaluated in
+    double, sums in double in a fixed order: bit-identical from run to run. Bad index entries /
+    labels address nothing, set bits 0 / 1 of ``status`` and make the loss NaN. Nothing of size
+    [N, C] is allocated. None where the kernels do not take the layout (``_sup_head_operands``):
+    the caller keeps torch's path."""
+    _require_device(z, labels, index, count, status)
+    if not _sup_head_operands(z, labels):
+        return None
+    if index is not None and count is not None:
+        raise ValueError("give the selection as index or as count, not both")
+    if index is not None and index.dtype != torch.int64:
+        raise TypeError(f"index must be int64 (got {index.dtype}); a mask goes through "
+                        "sup_head_count")
+    if index is not None and index.dim() != 1:
+        raise ValueError("index must be 1-D")
+    N, C = z.shape
+    if count is not None and (count.dtype != torch.int32 or count.shape != (N,)
+                              or not count.is_contiguous()):
+        raise ValueError(f"count must be a contiguous int32 [{N}] tensor")
+    lib = _lib.load()
+    dev = z.device
+    labels = labels.contiguous()
+    if index is not None:
+        index = index.contiguous()
+    n = N if index is None else index.shape[0]
+    if status is None:
+        status = _new_status(dev)
+    if n == 0:  # the mean of nothing
+        loss = torch.full((1,), float("nan"), dtype=torch.float32, device=dev)
+        correct = torch.zeros(1, dtype=torch.int64, device=dev) if want_correct else None
+        inv_valid = torch.full((1,), float("inf"), dtype=torch.float64, device=dev)
+    else:
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        correct = torch.empty(1, dtype=torch.int64, device=dev) if want_correct else None
+        inv_valid = torch.empty(1, dtype=torch.float64, device=dev)
+        ws = torch.empty(int(lib.gnn_sup_head_workspace_bytes(n)), dtype=torch.uint8, device=dev)
+        _lib.check(lib.gnn_sup_head_fwd_f32(
+            z.data_ptr(), z.stride(0) if N > 1 else C, labels.data_ptr(), _lib.ptr(index),
+            _lib.ptr(count), n, N, C, IGNORE_INDEX, loss.data_ptr(), _lib.ptr(correct),
+            inv_valid.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(),
+            _lib.stream_handle(dev)), "gnn_sup_head_fwd_f32")
+    return (loss.reshape(()), None if correct is None else correct.reshape(()), inv_valid,
+            status)
+
+
+def sup_head_backward(z: torch.Tensor, labels: torch.Tensor, count: torch.Tensor | None,
+                      upstream: torch.Tensor, inv_valid: torch.Tensor,
+                      status: torch.Tensor,
+                      out: torch.Tensor | None = None) -> torch.Tensor | None:
+    """The gradient of ``sup_head_forward``'s loss with respect to the whole z, contiguous
+    float32 [N, C] (gnn_sup_head_bwd_f32): one pass that writes every element once,
+    ``count[r] (softmax(z[r]) - onehot(labels[r])) upstream inv_valid`` recomputed from the
+    logits row in double, zeros for rows with count 0 or an ignored label (``count`` None:
+    every row once). ``upstream`` (float32, one element), ``inv_valid`` and ``status`` stay on
+    the device; a status that is not zero makes the whole gradient NaN. No zero fill, no
+    scatter, no [n, C] intermediate, no float atomics. ``out``: a float32 [N, C] view with unit
+    stride along C to write instead of a new tensor. None as ``sup_head_forward``."""
+    _require_device(z, labels, count, upstream, inv_valid, status, out)
+    if not _sup_head_operands(z, labels):
+        return None
+    N, C = z.shape
+    if out is not None and (out.shape != (N, C) or out.dtype != torch.float32
+                            or out.stride(1) != 1 or (N > 1 and out.stride(0) < C)):
+        raise ValueError(f"out must be a float32 [{N}, {C}] view with unit stride along C")
+    if upstream.dtype != torch.float32 or upstream.numel() != 1:
+        raise TypeError("upstream must be one float32 element")
+    if inv_valid.dtype != torch.float64 or inv_valid.numel() != 1:
+        raise TypeError("inv_valid must be one float64 element")
+    if status.dtype != torch.int32 or status.numel() != 1:
+        raise TypeError("status must be one int32 element")
+    if count is not None and (count.dtype != torch.int32 or count.shape != (N,)
+                              or not count.is_contiguous()):
+        raise ValueError(f"count must be a contiguous int32 [{N}] tensor")
+    lib = _lib.load()
+    dev = z.device
+    labels = labels.contiguous()
+    dz = out if out is not None else torch.empty((N, C), dtype=torch.float32, device=dev)
+    if N:
+        _lib.check(lib.gnn_sup_head_bwd_f32(
+            z.data_ptr(), z.stride(0) if N > 1 else C, labels.data_ptr(), _lib.ptr(count), N, C,
+            IGNORE_INDEX, upstream.data_ptr(), inv_valid.data_ptr(), status.data_ptr(),
+            dz.data_ptr(), dz.stride(0) if N > 1 else C, _lib.stream_handle(dev)),
+            "gnn_sup_head_bwd_f32")
+    return dz
+
+
 # The fused layer is opt-in (set SAGE_FUSED_MIN_ROWS to the smallest frontier to fuse): at
 # cfg4 it gains 2-3 % on layer 0 (62,479 rows: 110 vs 112 us) and loses on the 8,192-row
 # layer 1 (33 vs 25 us) -- its gathers and MFMAs do not overlap, so it costs about their

@@ -1306,6 +1306,54 @@ int gnn_bce_logits_f32(const float* z, int64_t ldz, const void* y, int64_t ldy, 
                        int64_t rows, int64_t cols, float* loss, float* g, int64_t ldg, void* ws,
                        int64_t ws_bytes, void* stream);
 
+/* ---- the head of the supervised training steps (sup_head.hip) ----
+ * GCN/train_eval.py:45-47, GAT/train_eval.py:73-75, GraphSAGE/train_eval.py:116-117:
+ * nn.CrossEntropyLoss()(output[idx], labels[idx]), the count behind accuracy() and the gradient
+ * with respect to the whole logits tensor. z: fp32 [N, C] logits (pitch ldz >= C, unit stride
+ * along C, 4-B aligned rows); labels: int64 [N]; row offsets are 64-bit. A row is evaluated in
+ * double (m = max_c z, lse = m + log sum_c exp(z_c - m), term = lse - z_y, p_c = exp(z_c - lse)),
+ * sums run in double in an order fixed by the shapes, every result is rounded once; non-finite
+ * logits give torch's results. No floating-point atomics: bit-identical from run to run.
+ *   gnn_sup_head_supported(C): 1 for C in [2, 64], else 0.
+ *   gnn_sup_head_count_index: count[N] (int32) = how often each row occurs in index[n] (int64,
+ *     entries in [-N, 0) wrap): count is zeroed on the stream, then integer atomic adds. An
+ *     entry outside [-N, N) addresses nothing and sets bit 0 of status[0], a device word the
+ *     caller zeroed. n < 2^31.
+ *   gnn_sup_head_count_mask: count[r] = mask[r] != 0 for a mask of N bytes.
+ *   gnn_sup_head_fwd_f32: the selection is index[n] (each entry one item, range-checked as
+ *     above; count must be NULL), or count[N] (row r taken count[r] times; n = N), or neither
+ *     (every row once; n = N). Rows whose label is ignore_index are left out of the sum and of
+ *     the denominator and are never correct. loss[0] = sum of the selected terms / n_valid
+ *     (NaN when n_valid = 0); n_correct[0] (nullable) = the number of selected items whose
+ *     label is the first maximum of their row, a NaN counting as the maximum
+ *     (torch.argmax); inv_valid[0] = 1 / n_valid. A selected row's label outside [0, C) that
+ *     is not ignore_index addresses nothing and sets bit 1 of status[0]; with status[0] != 0
+ *     the loss is NaN. `ws`: gnn_sup_head_workspace_bytes(n) bytes, 8-B aligned. Nothing of
+ *     size [N, C] is written. n = 0 returns GNN_OK with nothing launched: the mean of nothing
+ *     (NaN, 0 correct) is the caller's.
+ *   gnn_sup_head_bwd_f32: dz [N, C] (pitch lddz >= C), every element written exactly once:
+ *     dz[r, c] = count[r] (p_c - [c = y_r]) upstream[0] inv_valid[0], zero for rows with
+ *     count[r] = 0 or an ignored label; count NULL: every row once. upstream (the incoming
+ *     gradient of the loss), inv_valid and status are read on the device; with status[0] != 0
+ *     the whole gradient is NaN. N = 0 returns GNN_OK with nothing launched.
+ * Rejected before any launch: null operands and negative sizes (GNN_E_ARG), a pitch below C
+ * (GNN_E_ARG), a short workspace (GNN_E_ARG), misaligned pointers (GNN_E_ALIGN), a C that is
+ * not supported (GNN_E_UNSUPPORTED). */
+int gnn_sup_head_supported(int64_t C);
+int64_t gnn_sup_head_workspace_bytes(int64_t n);
+int gnn_sup_head_count_index(const int64_t* index, int64_t n, int64_t N, int32_t* count,
+                             uint32_t* status, void* stream);
+int gnn_sup_head_count_mask(const uint8_t* mask, int64_t N, int32_t* count, void* stream);
+int gnn_sup_head_fwd_f32(const float* z, int64_t ldz, const int64_t* labels,
+                         const int64_t* index, const int32_t* count, int64_t n, int64_t N,
+                         int64_t C, int64_t ignore_index, float* loss, int64_t* n_correct,
+                         double* inv_valid, uint32_t* status, void* ws, int64_t ws_bytes,
+                         void* stream);
+int gnn_sup_head_bwd_f32(const float* z, int64_t ldz, const int64_t* labels,
+                         const int32_t* count, int64_t N, int64_t C, int64_t ignore_index,
+                         const float* upstream, const double* inv_valid,
+                         const uint32_t* status, float* dz, int64_t lddz, void* stream);
+
 /*
  * Edge-cut halo exchange (SURVEY 8(b) gnn_halo_alltoallv; the all-to-all-v that
  * distributed.EdgeCutSpmm / EdgeCutGat run through torch.distributed on the nccl = RCCL
