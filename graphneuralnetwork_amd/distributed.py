@@ -454,12 +454,12 @@ def _cover_local_native(g: CsrGraph, rank: int, world: int, b: list):
     hp_rp, hp_col, hp_val = (torch.empty(n_own + 1, **i64), torch.empty(n_pk, **i32),
                              torch.empty(n_pk, **f32))
     P = _lib.ptr
-    _lib.check(lib.gnn_cover_fill(ws.data_ptr(), g.rowptr.data_ptr(), P(g.col), P(g.val), g.n_rows,
-                                  ctypes.addressof(hb), rank, world, ctypes.addressof(counts),
-                                  int_rp.data_ptr(), P(int_col), P(int_val), P(xcols),
-                                  hx_rp.data_ptr(), P(hx_col), P(hx_val), P(pe_i), P(pe_j),
-                                  P(pe_v), hp_rp.data_ptr(), P(hp_col), P(hp_val), stream),
-               "gnn_cover_fill")
+    _lib.run("gnn_cover_fill", workspace=ws.data_ptr(), rowptr=g.rowptr.data_ptr(), col=P(g.col),
+             val=P(g.val), n_rows=g.n_rows, bounds=ctypes.addressof(hb), rank=rank, world=world,
+             counts=ctypes.addressof(counts), int_rowptr=int_rp.data_ptr(), int_col=P(int_col),
+             int_val=P(int_val), xcols=P(xcols), hx_rowptr=hx_rp.data_ptr(), hx_col=P(hx_col),
+             hx_val=P(hx_val), pe_i=P(pe_i), pe_j=P(pe_j), pe_v=P(pe_v),
+             hp_rowptr=hp_rp.data_ptr(), hp_col=P(hp_col), hp_val=P(hp_val), stream=stream)
     interior = CsrGraph(int_rp, int_col, int_val, n_own, n_own)
     halo_x = CsrGraph(hx_rp, hx_col, hx_val, n_own, n_x)
     halo_p = CsrGraph(hp_rp, hp_col, hp_val, n_own, n_pk)

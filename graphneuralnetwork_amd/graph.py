@@ -104,18 +104,36 @@ class RowSplitPlan:
                                     self.small_val[keep].contiguous())
         return self._nonempty_small
 
-    def args(self, skip_empty: bool = False):
-        """The plan arguments of gnn_spmm_csr_f32 / gnn_gat_csr_f32 (after seg_len);
-        ``skip_empty`` drops the edgeless rows (see ``nonempty_small``)."""
-        from ._lib import ptr
+    # The plan arguments of the C-ABI entries, under the parameter names of gnn_mi355x.h
+    # (``_lib.invoke`` keywords).
+    def segments(self) -> dict:
+        """The long rows and their segments: every entry that takes a plan takes these."""
+        return dict(seg_len=self.seg_len, seg_row=self.seg_row.data_ptr(),
+                    seg_begin=self.seg_begin.data_ptr(), n_seg=self.n_seg,
+                    long_row=self.long_row.data_ptr(),
+                    long_seg_ptr=self.long_seg_ptr.data_ptr(), n_long=self.n_long)
+
+    def _mid(self, mid_row: torch.Tensor) -> dict:
+        # mid_row == NULL means "no plan" to the kernels, so a plan whose class is empty passes
+        # long_seg_ptr's address (never read: n_mid is 0)
+        n = int(mid_row.numel())
+        return dict(mid_row=mid_row.data_ptr() if n else self.long_seg_ptr.data_ptr(), n_mid=n)
+
+    def spmm_rows(self, skip_empty: bool = False) -> dict:
+        """The row classes of gnn_spmm_csr_* / gnn_spmm_csr_hub_*; ``skip_empty`` drops the
+        edgeless rows (see ``nonempty_small``)."""
         small_row, small_col, small_val = (self.nonempty_small() if skip_empty else
                                            (self.small_row, self.small_col, self.small_val))
-        return (ptr(self.seg_row), ptr(self.seg_begin), self.n_seg, ptr(self.long_row),
-                self.long_seg_ptr.data_ptr(), self.n_long, ptr(small_row),
-                ptr(small_col), ptr(small_val), int(small_row.numel()),
-                # mid_row must be non-NULL whenever a plan is used (NULL = "no plan")
-                self.mid_row.data_ptr() if self.n_mid else self.long_seg_ptr.data_ptr(),
-                self.n_mid)
+        return dict(small_row=small_row.data_ptr(), small_col=small_col.data_ptr(),
+                    small_val=small_val.data_ptr(), n_small=int(small_row.numel()),
+                    **self._mid(self.mid_row))
+
+    def gat_rows(self, mid: torch.Tensor, short: torch.Tensor) -> dict:
+        """The row classes of gnn_gat_csr_f32 / _hub_f32 / _ex_f32 for a ``gat_split``."""
+        n_short = int(short.numel())
+        return dict(small_row=self.small_row.data_ptr(), small_col=self.small_col.data_ptr(),
+                    n_small=self.n_small, **self._mid(mid),
+                    short_row=short.data_ptr() if n_short else None, n_short=n_short)
 
 
 # Packed row tasks (gnn_spmm_csr_tasks_f32): runs of consecutive rows of degree <= TASK_MAX_DEG
@@ -144,14 +162,14 @@ class TaskPlan:
     def n_mid(self) -> int:
         return int(self.mid_row.numel())
 
-    def args(self):
-        """The plan arguments of gnn_spmm_csr_tasks_f32 after seg_len."""
-        from ._lib import ptr
-        b = self.base
-        return (ptr(b.seg_row), ptr(b.seg_begin), b.n_seg, ptr(b.long_row),
-                b.long_seg_ptr.data_ptr(), b.n_long,
-                self.mid_row.data_ptr() if self.n_mid else b.long_seg_ptr.data_ptr(), self.n_mid,
-                self.task_row.data_ptr() if self.n_task else None, self.n_task)
+    def segments(self) -> dict:
+        return self.base.segments()
+
+    def task_rows(self) -> dict:
+        """The row classes of gnn_spmm_csr_tasks_* / gnn_gat_csr_tasks_f32."""
+        return dict(**self.base._mid(self.mid_row),
+                    task_row=self.task_row.data_ptr() if self.n_task else None,
+                    n_task=self.n_task)
 
 
 # The schedule builders run natively on the device (csrc/plan_build.hip: gnn_spmm_tasks_build,

@@ -153,49 +153,42 @@ def _tasks_ok(feat: int, *ts) -> bool:
         for t in ts)
 
 
-def _xh_f32(xh) -> int:
-    """The bf16 entries' ``xh_f32`` argument: 1 for an fp32 hub table (the XCD-direct partial
-    rows), 0 for a bf16 one or none."""
-    return int(xh is not None and xh.dtype == torch.float32)
+def _spmm_run(stem: str, g: CsrGraph, x, feat, bias, y, ldy, partial, flags, stream, **kw):
+    """Run ``stem``_f32 or ``stem``_bf16 (by x's element type) of the gnn_spmm_csr entries: the
+    operands every one of them takes and, in ``kw``, the entry's column array, plan and hub
+    table."""
+    _lib.run(stem + ("_bf16" if x.dtype == torch.bfloat16 else "_f32"),
+             rowptr=g.rowptr.data_ptr(), val=g.val.data_ptr(), n_rows=g.n_rows, x=x.data_ptr(),
+             ldx=x.stride(0), feat=feat, bias=_lib.ptr(bias), y=y.data_ptr(), ldy=ldy,
+             partial=_lib.ptr(partial), flags=flags, stream=stream, **kw)
 
 
-def _spmm_tasks_call(lib, g: CsrGraph, col: torch.Tensor, tp, x, xh, feat, bias, y, ldy,
-                     partial, flags, stream, what):
+def _hub_table(x, xh) -> dict:
+    """The hub table of the hub / tasks entries (None: no table). The bf16 entries also take its
+    element type: ``xh_f32`` = 1 for an fp32 table (the XCD-direct partial rows), 0 for a bf16
+    one or none."""
+    kw = dict(xh=_lib.ptr(xh), ldh=xh.stride(0) if xh is not None else 0)
     if x.dtype == torch.bfloat16:
-        _lib.check(lib.gnn_spmm_csr_tasks_bf16(
-            g.rowptr.data_ptr(), col.data_ptr(), g.val.data_ptr(), g.n_rows, x.data_ptr(),
-            x.stride(0), _lib.ptr(xh), xh.stride(0) if xh is not None else 0, _xh_f32(xh), feat,
-            _lib.ptr(bias), y.data_ptr(), ldy, tp.seg_len, *tp.args(), _lib.ptr(partial), flags,
-            stream), what.replace("_f32", "_bf16"))
-        return
-    _lib.check(lib.gnn_spmm_csr_tasks_f32(
-        g.rowptr.data_ptr(), col.data_ptr(), g.val.data_ptr(), g.n_rows, x.data_ptr(),
-        x.stride(0), _lib.ptr(xh), xh.stride(0) if xh is not None else 0, feat, _lib.ptr(bias),
-        y.data_ptr(), ldy, tp.seg_len, *tp.args(), _lib.ptr(partial), flags, stream), what)
+        kw["xh_f32"] = int(xh is not None and xh.dtype == torch.float32)
+    return kw
 
 
-def _spmm_hub_call(lib, g: CsrGraph, col: torch.Tensor, plan, pargs, x, xh, feat, bias, y, ldy,
-                   partial, flags, stream, what):
-    if x.dtype == torch.bfloat16:
-        _lib.check(lib.gnn_spmm_csr_hub_bf16(
-            g.rowptr.data_ptr(), col.data_ptr(), g.val.data_ptr(), g.n_rows, x.data_ptr(),
-            x.stride(0), xh.data_ptr(), xh.stride(0), _xh_f32(xh), feat, _lib.ptr(bias),
-            y.data_ptr(), ldy, plan.seg_len, *pargs, _lib.ptr(partial), flags, stream),
-            what.replace("_f32", "_bf16"))
-        return
-    _lib.check(lib.gnn_spmm_csr_hub_f32(
-        g.rowptr.data_ptr(), col.data_ptr(), g.val.data_ptr(), g.n_rows, x.data_ptr(),
-        x.stride(0), xh.data_ptr(), xh.stride(0), feat, _lib.ptr(bias), y.data_ptr(), ldy,
-        plan.seg_len, *pargs, _lib.ptr(partial), flags, stream), what)
+def _spmm_tasks_call(g: CsrGraph, col: torch.Tensor, tp, x, xh, feat, bias, y, ldy, partial,
+                     flags, stream):
+    _spmm_run("gnn_spmm_csr_tasks", g, x, feat, bias, y, ldy, partial, flags, stream,
+              col=col.data_ptr(), **_hub_table(x, xh), **tp.segments(), **tp.task_rows())
 
 
-def _spmm_plain_call(lib, g: CsrGraph, plan, pargs, x, feat, bias, y, ldy, partial, flags, stream,
-                     what):
-    fn = lib.gnn_spmm_csr_bf16 if x.dtype == torch.bfloat16 else lib.gnn_spmm_csr_f32
-    _lib.check(fn(g.rowptr.data_ptr(), g.col.data_ptr(), g.val.data_ptr(), g.n_rows,
-                  x.data_ptr(), x.stride(0), feat, _lib.ptr(bias), y.data_ptr(), ldy,
-                  plan.seg_len, *pargs, _lib.ptr(partial), flags, stream),
-               what.replace("_f32", "_bf16") if x.dtype == torch.bfloat16 else what)
+def _spmm_hub_call(g: CsrGraph, col: torch.Tensor, plan, skip_empty, x, xh, feat, bias, y, ldy,
+                   partial, flags, stream):
+    _spmm_run("gnn_spmm_csr_hub", g, x, feat, bias, y, ldy, partial, flags, stream,
+              col_hub=col.data_ptr(), **_hub_table(x, xh), **plan.segments(),
+              **plan.spmm_rows(skip_empty))
+
+
+def _spmm_plain_call(g: CsrGraph, plan, skip_empty, x, feat, bias, y, ldy, partial, flags, stream):
+    _spmm_run("gnn_spmm_csr", g, x, feat, bias, y, ldy, partial, flags, stream,
+              col=g.col.data_ptr(), **plan.segments(), **plan.spmm_rows(skip_empty))
 
 
 def _gather_hub_rows(lib, x, hub_ids, k, feat, out, err, stream):
@@ -283,7 +276,6 @@ def spmm_forward(g: CsrGraph, x: torch.Tensor, bias: torch.Tensor | None = None,
     partial = None
     if plan.n_seg:
         partial = torch.empty((plan.n_seg, feat), dtype=torch.float32, device=x.device)
-    pargs = plan.args(skip_empty=skip_empty)
     k = hub_rows_for(g.n_cols, feat, esize) if hubs is None else min(int(hubs), g.n_cols)
     tasks = _tasks_ok(feat, x, out, bias, partial)
     if k > 0 and g.nnz:
@@ -294,25 +286,20 @@ def spmm_forward(g: CsrGraph, x: torch.Tensor, bias: torch.Tensor | None = None,
             xh = torch.empty((hp.k, feat), dtype=x.dtype, device=x.device)
             _gather_hub_rows(lib, x, hp.hub_ids, hp.k, feat, xh, hp.err, stream)
         if tasks:
-            gh = CsrGraph(g.rowptr, hp.col_hub, g.val, g.n_rows, g.n_cols)
-            _spmm_tasks_call(lib, gh, hp.col_hub,
-                             g.task_plan(seg, TASK_MAX_DEG, _task_cost(feat)), x,
-                             xh, feat, bias, out, out.stride(0), partial,
-                             flags | (_lib.EPI_SKIP_EMPTY if skip_empty else 0), stream,
-                             "gnn_spmm_csr_tasks_f32 (hub)")
+            _spmm_tasks_call(g, hp.col_hub, g.task_plan(seg, TASK_MAX_DEG, _task_cost(feat)),
+                             x, xh, feat, bias, out, out.stride(0), partial,
+                             flags | (_lib.EPI_SKIP_EMPTY if skip_empty else 0), stream)
             return out
-        _spmm_hub_call(lib, g, hp.col_hub, plan, pargs, x, xh, feat, bias, out, out.stride(0),
-                       partial, flags, stream, "gnn_spmm_csr_hub_f32")
+        _spmm_hub_call(g, hp.col_hub, plan, skip_empty, x, xh, feat, bias, out, out.stride(0),
+                       partial, flags, stream)
         return out
     if tasks and g.nnz:
-        _spmm_tasks_call(lib, g, g.col, g.task_plan(seg, TASK_MAX_DEG, _task_cost(feat)), x,
-                         None, feat,
-                         bias, out, out.stride(0), partial,
-                         flags | (_lib.EPI_SKIP_EMPTY if skip_empty else 0), stream,
-                         "gnn_spmm_csr_tasks_f32")
+        _spmm_tasks_call(g, g.col, g.task_plan(seg, TASK_MAX_DEG, _task_cost(feat)), x, None,
+                         feat, bias, out, out.stride(0), partial,
+                         flags | (_lib.EPI_SKIP_EMPTY if skip_empty else 0), stream)
         return out
-    _spmm_plain_call(lib, g, plan, pargs, x, feat, bias, out, out.stride(0), partial, flags,
-                     stream, "gnn_spmm_csr_f32")
+    _spmm_plain_call(g, plan, skip_empty, x, feat, bias, out, out.stride(0), partial, flags,
+                     stream)
     return out
 
 
@@ -322,7 +309,7 @@ def _spmm_xcd(lib, g: CsrGraph, xp, x, feat, bias, out, seg, skip_empty, flags, 
     edges + partial refs, with the epilogue). Three launches on one stream."""
     k, n_pos = xp.k, xp.n_pos
     if XCD_DIRECT and xp.prefix:
-        _spmm_xcd_direct(lib, xp, x, feat, bias, out, seg, skip_empty, flags, stream)
+        _spmm_xcd_direct(xp, x, feat, bias, out, seg, skip_empty, flags, stream)
         return
     buf = torch.empty((k + n_pos, feat), dtype=torch.float32, device=x.device)
     hp = xp.hub
@@ -332,24 +319,22 @@ def _spmm_xcd(lib, g: CsrGraph, xp, x, feat, bias, out, seg, skip_empty, flags, 
     p1 = xp.items.plan(seg)
     if p1.n_seg or p1.n_small:  # by construction every item is a 2..chunk-edge row
         raise RuntimeError("XCD hub plan: item rows outside the mid-row class")
-    _spmm_hub_call(lib, xp.items, xp.items.col, p1, p1.args(), x, buf, feat, None, buf[k:], feat,
-                   None, 0, stream, "gnn_spmm_csr_hub_f32 (xcd items)")
+    _spmm_hub_call(xp.items, xp.items.col, p1, False, x, buf, feat, None, buf[k:], feat, None, 0,
+                   stream)
     if _tasks_ok(feat, x, out, bias, buf):
         tp = xp.rest.task_plan(seg, TASK_MAX_DEG, _task_cost(feat))
         partial = None
         if tp.base.n_seg:
             partial = torch.empty((tp.base.n_seg, feat), dtype=torch.float32, device=x.device)
-        _spmm_tasks_call(lib, xp.rest, xp.rest.col, tp, x, buf, feat, bias, out, out.stride(0),
-                         partial, flags | (_lib.EPI_SKIP_EMPTY if skip_empty else 0), stream,
-                         "gnn_spmm_csr_tasks_f32 (xcd rest)")
+        _spmm_tasks_call(xp.rest, xp.rest.col, tp, x, buf, feat, bias, out, out.stride(0),
+                         partial, flags | (_lib.EPI_SKIP_EMPTY if skip_empty else 0), stream)
         return
     p2 = xp.rest_plan(seg)
     partial = None
     if p2.n_seg:
         partial = torch.empty((p2.n_seg, feat), dtype=torch.float32, device=x.device)
-    _spmm_hub_call(lib, xp.rest, xp.rest.col, p2, p2.args(skip_empty=skip_empty), x, buf, feat,
-                   bias, out, out.stride(0), partial, flags, stream,
-                   "gnn_spmm_csr_hub_f32 (xcd rest)")
+    _spmm_hub_call(xp.rest, xp.rest.col, p2, skip_empty, x, buf, feat, bias, out, out.stride(0),
+                   partial, flags, stream)
 
 
 # Storage type of the support tensor S = X W^T between Graph_conv_layer's transform and its
@@ -590,7 +575,7 @@ def model_dropout(x: torch.Tensor, p: float, training: bool, perm=None, inv=None
     return DropoutRows.apply(x, p, dropout_seed(), perm, inv)
 
 
-def _spmm_xcd_direct(lib, xp, x, feat, bias, out, seg, skip_empty, flags, stream):
+def _spmm_xcd_direct(xp, x, feat, bias, out, seg, skip_empty, flags, stream):
     """The XCD-sliced SpMM of a degree-ordered graph (graph.degree_order): the hub rows are
     X's first k rows, so there is no staging copy. Pass 1 (plain kernel) reads the items'
     hub rows from X into a partial-row buffer; pass 2 reads X and that buffer (c < 0 ->
@@ -601,24 +586,21 @@ def _spmm_xcd_direct(lib, xp, x, feat, bias, out, seg, skip_empty, flags, stream
     p1 = items.plan(seg)
     if p1.n_seg or p1.n_small:
         raise RuntimeError("XCD hub plan: item rows outside the mid-row class")
-    _spmm_plain_call(lib, items, p1, p1.args(), x, feat, None, part, feat, None, 0, stream,
-                     "gnn_spmm_csr_f32 (xcd direct items)")
+    _spmm_plain_call(items, p1, False, x, feat, None, part, feat, None, 0, stream)
     if _tasks_ok(feat, x, out, bias, part):
         tp = rest.task_plan(seg, TASK_MAX_DEG, _task_cost(feat))
         partial = None
         if tp.base.n_seg:
             partial = torch.empty((tp.base.n_seg, feat), dtype=torch.float32, device=x.device)
-        _spmm_tasks_call(lib, rest, rest.col, tp, x, part, feat, bias, out, out.stride(0),
-                         partial, flags | (_lib.EPI_SKIP_EMPTY if skip_empty else 0), stream,
-                         "gnn_spmm_csr_tasks_f32 (xcd direct rest)")
+        _spmm_tasks_call(rest, rest.col, tp, x, part, feat, bias, out, out.stride(0), partial,
+                         flags | (_lib.EPI_SKIP_EMPTY if skip_empty else 0), stream)
         return
     p2 = staged_plan(rest, seg)
     partial = None
     if p2.n_seg:
         partial = torch.empty((p2.n_seg, feat), dtype=torch.float32, device=x.device)
-    _spmm_hub_call(lib, rest, rest.col, p2, p2.args(skip_empty=skip_empty), x, part, feat, bias,
-                   out, out.stride(0), partial, flags, stream,
-                   "gnn_spmm_csr_hub_f32 (xcd direct rest)")
+    _spmm_hub_call(rest, rest.col, p2, skip_empty, x, part, feat, bias, out, out.stride(0),
+                   partial, flags, stream)
 
 
 class _SpmmFn(torch.autograd.Function):
@@ -1293,17 +1275,24 @@ def _gat_tasks_ok(heads, fh, *ts) -> bool:
 GAT_XCD = False
 
 
-def _gat_call(lib, g_rowptr, col, n, wh, el, er, lde, heads, fh, slope, mode, fill, out, ldo,
-              seg_len, plan, mid, short, partial, stats, flags, stream, whh, erh, what):
-    pa = plan.args()
-    _lib.check(lib.gnn_gat_csr_hub_f32(
-        g_rowptr.data_ptr(), col.data_ptr(), n, wh.data_ptr(), wh.stride(0), heads, fh,
-        el.data_ptr(), er.data_ptr(), lde, float(slope), int(mode), _lib.ptr(fill), 0.0, 0,
-        out.data_ptr(), ldo, seg_len, *pa[:6], pa[6], pa[7], pa[9],
-        mid.data_ptr() if mid.numel() else pa[10], mid.numel(),
-        short.data_ptr() if short is not None and short.numel() else None,
-        short.numel() if short is not None else 0, _lib.ptr(partial), _lib.ptr(stats), flags,
-        stream, whh.data_ptr(), whh.stride(0), erh.data_ptr(), erh.stride(0)), what)
+def _gat_operands(rowptr, n, wh, el, er, lde, heads, fh, slope, mode, fill, out, ldo, partial,
+                  stats, flags, stream, dropout_p=0.0, seed=0) -> dict:
+    """The arguments every gnn_gat_csr_* entry takes, but for its column array and plan."""
+    return dict(rowptr=rowptr.data_ptr(), n_rows=n, wh=wh.data_ptr(), ldw=wh.stride(0),
+                heads=heads, fh=fh, el=el.data_ptr(), er=er.data_ptr(), lde=lde,
+                negative_slope=float(slope), mode=int(mode), empty_row_fill=_lib.ptr(fill),
+                dropout_p=float(dropout_p), dropout_seed=int(seed) & 0xFFFFFFFFFFFFFFFF,
+                out=out.data_ptr(), ldo=ldo, partial=_lib.ptr(partial), stats=_lib.ptr(stats),
+                flags=flags, stream=stream)
+
+
+def _gat_call(g_rowptr, col, n, wh, el, er, lde, heads, fh, slope, mode, fill, out, ldo, plan,
+              mid, short, partial, stats, flags, stream, whh, erh):
+    _lib.run("gnn_gat_csr_hub_f32", col_hub=col.data_ptr(),
+             **_gat_operands(g_rowptr, n, wh, el, er, lde, heads, fh, slope, mode, fill, out, ldo,
+                             partial, stats, flags, stream),
+             **plan.segments(), **plan.gat_rows(mid, short), whh=whh.data_ptr(),
+             ldwh=whh.stride(0), erh=erh.data_ptr(), ldeh=erh.stride(0))
 
 
 def _gat_xcd(lib, g: CsrGraph, xp, wh, el, er, heads, fh, slope, mode, fill, out, seg, flags,
@@ -1334,9 +1323,9 @@ def _gat_xcd(lib, g: CsrGraph, xp, wh, el, er, heads, fh, slope, mode, fill, out
     if p1.n_seg or p1.n_small:
         raise RuntimeError("XCD hub plan: item rows outside the mid-row class")
     # er is never read in pass 1 (every column is staged): erb stands in with its stride
-    _gat_call(lib, xp.items.rowptr, xp.items.col, n_pos, wh, el_items, erb, heads, heads, fh,
-              slope, mode, None, whb[k:], feat, seg, p1, p1.mid_row, None, None, lse, 0, stream,
-              whb, erb, "gnn_gat_csr_hub_f32 (xcd items)")
+    _gat_call(xp.items.rowptr, xp.items.col, n_pos, wh, el_items, erb, heads, heads, fh, slope,
+              mode, None, whb[k:], feat, p1, p1.mid_row, p1.mid_row[:0], None, lse, 0, stream,
+              whb, erb)
     y = lse if mode == GAT_DENSE else -lse
     torch.sub(torch.where(y >= 0, y, y / slope), el_items, out=erb[k:])
     p2 = xp.rest_plan(seg)
@@ -1344,9 +1333,9 @@ def _gat_xcd(lib, g: CsrGraph, xp, wh, el, er, heads, fh, slope, mode, fill, out
     partial = None
     if p2.n_seg:
         partial = torch.empty((p2.n_seg, feat + 2 * heads), dtype=torch.float32, device=dev)
-    _gat_call(lib, xp.rest.rowptr, xp.rest.col, g.n_rows, wh, el, er, el.stride(0), heads, fh,
-              slope, mode, fill, out, out.stride(0), seg, p2, mid, short, partial, None, flags,
-              stream, whb, erb, "gnn_gat_csr_hub_f32 (xcd rest)")
+    _gat_call(xp.rest.rowptr, xp.rest.col, g.n_rows, wh, el, er, el.stride(0), heads, fh, slope,
+              mode, fill, out, out.stride(0), p2, mid, short, partial, None, flags, stream, whb,
+              erb)
 
 
 def gat_aggregate_staged(g: CsrGraph, wh: torch.Tensor, el: torch.Tensor, er: torch.Tensor,
@@ -1398,10 +1387,9 @@ def gat_aggregate_staged(g: CsrGraph, wh: torch.Tensor, el: torch.Tensor, er: to
     if plan.n_seg:
         partial = torch.empty((plan.n_seg, feat + 2 * heads), dtype=torch.float32,
                               device=wh.device)
-    _gat_call(_lib.load(), g.rowptr, g.col, g.n_rows, wh, el, er, el.stride(0), heads, fh,
-              negative_slope, mode, None, out, out.stride(0), seg, plan, mid, short, partial,
-              None, _ACT_FLAGS[activation], _lib.stream_handle(wh.device), whh, erh,
-              "gnn_gat_csr_hub_f32 (staged)")
+    _gat_call(g.rowptr, g.col, g.n_rows, wh, el, er, el.stride(0), heads, fh, negative_slope,
+              mode, None, out, out.stride(0), plan, mid, short, partial, None,
+              _ACT_FLAGS[activation], _lib.stream_handle(wh.device), whh, erh)
     return out
 
 
@@ -1464,17 +1452,12 @@ def gat_aggregate(g: CsrGraph, wh: torch.Tensor, el: torch.Tensor, er: torch.Ten
     if plan.n_seg:
         partial = torch.empty((plan.n_seg, feat + 2 * heads), dtype=torch.float32,
                               device=wh.device)
-    pa = plan.args()  # (seg_row, seg_begin, n_seg, long_row, long_seg_ptr, n_long,
-    #                    small_row, small_col, small_val, n_small, mid_row, n_mid)
     mid, short = plan.gat_split(g.rowptr, GAT_SHORT_MAX_DEG)
     stream = _lib.stream_handle(wh.device)
-    args = (n, wh.data_ptr(), wh.stride(0), heads, fh,
-            el.data_ptr(), er.data_ptr(), lde, float(negative_slope), int(mode), _lib.ptr(fill),
-            float(dropout_p), int(seed) & 0xFFFFFFFFFFFFFFFF, out.data_ptr(), out.stride(0),
-            plan.seg_len, *pa[:6], pa[6], pa[7], pa[9],
-            mid.data_ptr() if mid.numel() else pa[10], mid.numel(),
-            short.data_ptr() if short.numel() else None, short.numel(), _lib.ptr(partial),
-            _lib.ptr(stats), _ACT_FLAGS[activation], stream)
+    kw = _gat_operands(g.rowptr, n, wh, el, er, lde, heads, fh, negative_slope, mode, fill, out,
+                       out.stride(0), partial, stats, _ACT_FLAGS[activation], stream, dropout_p,
+                       seed)
+    kw.update(plan.segments())
     k = hub_rows_for(g.n_cols, feat + heads) if hubs is None else min(int(hubs), g.n_cols)
     hp = whh = erh = None
     ldwh = lderh = 0
@@ -1492,42 +1475,28 @@ def gat_aggregate(g: CsrGraph, wh: torch.Tensor, el: torch.Tensor, er: torch.Ten
                                                    dst.data_ptr(), w, hp.err.data_ptr(), stream),
                            "gnn_gather_rows_f32")
     col = hp.col_hub if hp is not None else g.col
+    staged = dict(whh=_lib.ptr(whh), ldwh=ldwh, erh=_lib.ptr(erh), ldeh=lderh)
     if _gat_tasks_ok(heads, fh, wh, out, fill, whh):
+        # the task plan's segments are ``plan``'s own (its base is the cached g.plan(seg))
         tp = g.task_plan(plan.seg_len, GAT_SHORT_MAX_DEG, GAT_TASK_COST)
-        b = tp.base
-        if b.n_seg and partial is None:
-            partial = torch.empty((b.n_seg, feat + 2 * heads), dtype=torch.float32,
-                                  device=wh.device)
-        rc = lib.gnn_gat_csr_tasks_f32(
-            g.rowptr.data_ptr(), col.data_ptr(), n, wh.data_ptr(), wh.stride(0), heads, fh,
-            el.data_ptr(), er.data_ptr(), lde, float(negative_slope), int(mode), _lib.ptr(fill),
-            float(dropout_p), int(seed) & 0xFFFFFFFFFFFFFFFF, out.data_ptr(), out.stride(0),
-            tp.seg_len, _lib.ptr(b.seg_row), _lib.ptr(b.seg_begin), b.n_seg, _lib.ptr(b.long_row),
-            b.long_seg_ptr.data_ptr(), b.n_long,
-            tp.mid_row.data_ptr() if tp.n_mid else b.long_seg_ptr.data_ptr(), tp.n_mid,
-            tp.task_row.data_ptr() if tp.n_task else None, tp.n_task, _lib.ptr(partial),
-            _lib.ptr(stats), _ACT_FLAGS[activation], stream, _lib.ptr(whh), ldwh, _lib.ptr(erh),
-            lderh)
+        rc = _lib.invoke("gnn_gat_csr_tasks_f32", col=col.data_ptr(), **kw, **tp.task_rows(),
+                         **staged)
         if rc != _lib.E_UNSUPPORTED:  # e.g. a 4-float vector path the row pitches do not allow
             _lib.check(rc, "gnn_gat_csr_tasks_f32")
             return out
         # the row-class launch below (same plan, same partial buffer) covers the shape
+    kw.update(plan.gat_rows(mid, short))
     if a_dst is not None and GAT_ER_RECOMPUTE:
         a_dst = a_dst.detach().reshape(-1).contiguous().float()
         if a_dst.numel() != feat:
             raise ValueError("a_dst must hold heads * fh values")
         _require_device(a_dst)
-        rc = lib.gnn_gat_csr_ex_f32(g.rowptr.data_ptr(), col.data_ptr(), *args, _lib.ptr(whh),
-                                    ldwh, _lib.ptr(erh), lderh, a_dst.data_ptr())
-        _lib.check(rc, "gnn_gat_csr_ex_f32")
-        return out
-    if hp is not None:
-        rc = lib.gnn_gat_csr_hub_f32(g.rowptr.data_ptr(), hp.col_hub.data_ptr(), *args,
-                                     whh.data_ptr(), ldwh, erh.data_ptr(), lderh)
-        _lib.check(rc, "gnn_gat_csr_hub_f32")
-        return out
-    rc = lib.gnn_gat_csr_f32(g.rowptr.data_ptr(), g.col.data_ptr(), *args)
-    _lib.check(rc, "gnn_gat_csr_f32")
+        _lib.run("gnn_gat_csr_ex_f32", col=col.data_ptr(), **kw, **staged,
+                 a_dst=a_dst.data_ptr())
+    elif hp is not None:
+        _lib.run("gnn_gat_csr_hub_f32", col_hub=col.data_ptr(), **kw, **staged)
+    else:
+        _lib.run("gnn_gat_csr_f32", col=col.data_ptr(), **kw)
     return out
 
 
@@ -2538,7 +2507,6 @@ def _gat_backward_recompute(g, wh, el, er, stats, y, dy, a_src, a_dst, heads, fh
     if not _bwd_recompute_ok(heads, fh, wh.stride(0)):
         return None
     dev = wh.device
-    lib = _lib.load()
     stream = _lib.stream_handle(dev)
     f32 = dict(dtype=torch.float32, device=dev)
     sl = seg_len if seg_len is not None else seg_len_for(feat, GAT_SEG_BYTES)
@@ -2556,16 +2524,16 @@ def _gat_backward_recompute(g, wh, el, er, stats, y, dy, a_src, a_dst, heads, fh
     mark("rows")
 
     def rows_pass(dy, dp, ds):
-        return lib.gnn_gat_backward_rows_ex_f32(
-            g.rowptr.data_ptr(), g.col.data_ptr(), n, wh.data_ptr(), wh.stride(0), heads, fh,
-            el.data_ptr(), er.data_ptr(), stats.data_ptr(), dy.data_ptr(), y.data_ptr(), feat,
-            int(elu), float(negative_slope), int(mode), float(dropout_p), seed64,
-            dout.data_ptr(), nstat.data_ptr(), dl.data_ptr(), plan.seg_len,
-            _lib.ptr(plan.seg_row), _lib.ptr(plan.seg_begin), plan.n_seg,
-            _lib.ptr(plan.long_row), plan.long_seg_ptr.data_ptr(), plan.n_long, _lib.ptr(rows),
-            rows.numel(), _lib.ptr(short), short.numel(), del_part.data_ptr(),
-            a_dst.data_ptr() if GAT_ER_RECOMPUTE else None, float(dp),
-            int(ds) & 0xFFFFFFFFFFFFFFFF, stream)
+        return _lib.invoke(
+            "gnn_gat_backward_rows_ex_f32", rowptr=g.rowptr.data_ptr(), col=g.col.data_ptr(),
+            n_rows=n, wh=wh.data_ptr(), ldw=wh.stride(0), heads=heads, fh=fh, el=el.data_ptr(),
+            er=er.data_ptr(), lse=stats.data_ptr(), dy=dy.data_ptr(), y=y.data_ptr(), ldo=feat,
+            elu=int(elu), negative_slope=float(negative_slope), mode=int(mode),
+            dropout_p=float(dropout_p), dropout_seed=seed64, dout=dout.data_ptr(),
+            nstat=nstat.data_ptr(), d_el=dl.data_ptr(), **plan.segments(), rows=rows.data_ptr(),
+            n_rows_list=rows.numel(), short_rows=short.data_ptr(), n_short=short.numel(),
+            del_part=del_part.data_ptr(), a_dst=a_dst.data_ptr() if GAT_ER_RECOMPUTE else None,
+            dy_dropout_p=float(dp), dy_dropout_seed=int(ds) & 0xFFFFFFFFFFFFFFFF, stream=stream)
 
     if dy_dropout is not None:  # the upstream mask inside the prep where it takes the shape
         rc = rows_pass(dy, dy_dropout[0], dy_dropout[1])
@@ -2588,14 +2556,15 @@ def _gat_backward_recompute(g, wh, el, er, stats, y, dy, a_src, a_dst, heads, fh
     der = torch.empty((n, heads), **f32)
     part = torch.empty((max(pt.n_seg, 1), feat + heads), **f32)
     mark("nodes")
-    rc = lib.gnn_gat_backward_nodes_recompute_f32(
-        rowptr_t.data_ptr(), src_t.data_ptr(), _lib.ptr(eid_t), n, heads, fh, dout.data_ptr(),
-        nstat.data_ptr(), wh.data_ptr(), wh.stride(0), er.data_ptr(), dl.data_ptr(),
-        a_src.data_ptr(), a_dst.data_ptr(), float(negative_slope), int(mode), float(dropout_p),
-        seed64, dwh.data_ptr(), der.data_ptr(), pt.seg_len, _lib.ptr(pt.seg_row),
-        _lib.ptr(pt.seg_begin), pt.n_seg, _lib.ptr(pt.long_row), pt.long_seg_ptr.data_ptr(),
-        pt.n_long, _lib.ptr(rows_t), rows_t.numel(), _lib.ptr(short_t), short_t.numel(),
-        part.data_ptr(), stream)
+    rc = _lib.invoke(
+        "gnn_gat_backward_nodes_recompute_f32", rowptr_t=rowptr_t.data_ptr(),
+        src_t=src_t.data_ptr(), eid_t=_lib.ptr(eid_t), n_nodes=n, heads=heads, fh=fh,
+        dout=dout.data_ptr(), nstat=nstat.data_ptr(), wh=wh.data_ptr(), ldw=wh.stride(0),
+        er=er.data_ptr(), d_el=dl.data_ptr(), a_src=a_src.data_ptr(), a_dst=a_dst.data_ptr(),
+        negative_slope=float(negative_slope), mode=int(mode), dropout_p=float(dropout_p),
+        dropout_seed=seed64, dwh=dwh.data_ptr(), der=der.data_ptr(), **pt.segments(),
+        rows=rows_t.data_ptr(), n_rows_list=rows_t.numel(), short_rows=short_t.data_ptr(),
+        n_short=short_t.numel(), part=part.data_ptr(), stream=stream)
     if rc == _lib.E_UNSUPPORTED:
         # the row pass's outputs are the three-pass path's prep + edge outputs but for w / ds:
         # start over there (a shape both refuse is one the three-pass kernels also cover)
@@ -2661,14 +2630,14 @@ def gat_backward(g: CsrGraph, wh: torch.Tensor, el: torch.Tensor, er: torch.Tens
     del_part = torch.empty((max(plan.n_seg, 1), heads), dtype=torch.float32, device=dev)
     rows = plan.row_list()
     mark("edges")
-    _lib.check(lib.gnn_gat_backward_edges_f32(
-        g.rowptr.data_ptr(), g.col.data_ptr(), n, wh.data_ptr(), wh.stride(0), heads, fh,
-        el.data_ptr(), er.data_ptr(), stats.data_ptr(), dout.data_ptr(), D.data_ptr(),
-        float(negative_slope), int(mode), float(dropout_p), int(seed) & 0xFFFFFFFFFFFFFFFF,
-        w_edge.data_ptr(), ds_edge.data_ptr(), dl.data_ptr(), plan.seg_len,
-        _lib.ptr(plan.seg_row), _lib.ptr(plan.seg_begin), plan.n_seg, _lib.ptr(plan.long_row),
-        plan.long_seg_ptr.data_ptr(), plan.n_long, _lib.ptr(rows), rows.numel(),
-        del_part.data_ptr(), stream), "gnn_gat_backward_edges_f32")
+    _lib.run(
+        "gnn_gat_backward_edges_f32", rowptr=g.rowptr.data_ptr(), col=g.col.data_ptr(), n_rows=n,
+        wh=wh.data_ptr(), ldw=wh.stride(0), heads=heads, fh=fh, el=el.data_ptr(),
+        er=er.data_ptr(), lse=stats.data_ptr(), dout=dout.data_ptr(), D=D.data_ptr(),
+        negative_slope=float(negative_slope), mode=int(mode), dropout_p=float(dropout_p),
+        dropout_seed=int(seed) & 0xFFFFFFFFFFFFFFFF, w_edge=w_edge.data_ptr(),
+        ds_edge=ds_edge.data_ptr(), d_el=dl.data_ptr(), **plan.segments(), rows=rows.data_ptr(),
+        n_rows_list=rows.numel(), del_part=del_part.data_ptr(), stream=stream)
     rowptr_t, src_t, eid_t, gt = g.transpose_eid()
     pt = gt.plan(sl)
     rows_t = pt.row_list()
@@ -2679,12 +2648,12 @@ def gat_backward(g: CsrGraph, wh: torch.Tensor, el: torch.Tensor, er: torch.Tens
     a_dst = a_dst.contiguous().float()
     # one node pass for every head (the kernel sums der over groups of 8 heads itself)
     mark("nodes")
-    _lib.check(lib.gnn_gat_backward_nodes_f32(
-        rowptr_t.data_ptr(), src_t.data_ptr(), eid_t.data_ptr(), n, heads, fh,
-        dout.data_ptr(), w_edge.data_ptr(), ds_edge.data_ptr(), dl.data_ptr(),
-        a_src.data_ptr(), a_dst.data_ptr(), dwh.data_ptr(), der.data_ptr(), pt.seg_len,
-        _lib.ptr(pt.seg_row), _lib.ptr(pt.seg_begin), pt.n_seg, _lib.ptr(pt.long_row),
-        pt.long_seg_ptr.data_ptr(), pt.n_long, _lib.ptr(rows_t), rows_t.numel(),
-        part.data_ptr(), stream), "gnn_gat_backward_nodes_f32")
+    _lib.run(
+        "gnn_gat_backward_nodes_f32", rowptr_t=rowptr_t.data_ptr(), src_t=src_t.data_ptr(),
+        eid_t=eid_t.data_ptr(), n_nodes=n, heads=heads, fh=fh, dout=dout.data_ptr(),
+        w_edge=w_edge.data_ptr(), ds_edge=ds_edge.data_ptr(), d_el=dl.data_ptr(),
+        a_src=a_src.data_ptr(), a_dst=a_dst.data_ptr(), dwh=dwh.data_ptr(), der=der.data_ptr(),
+        **pt.segments(), rows=rows_t.data_ptr(), n_rows_list=rows_t.numel(),
+        part=part.data_ptr(), stream=stream)
     mark(None)
     return dwh, dout, dl, der

@@ -688,10 +688,10 @@ int gnn_col_mean_f32(const float* x, int64_t ldx, int64_t n_rows, int64_t feat, 
  * prep : dout = dy * ELU'(out) (elu != 0; out recovered from y), D_i = dout_i . out_i
  *        (dout [n, heads*fh], D [n, heads]);
  * edges: over CSR rows (plan segments + `rows` = every other row), per edge e and head:
- *        w_edge[e,h] = m a, ds_edge[e,h] = a (m dout_i.Wh_j - D_i) dz/ds, del[i,h] = sum_e ds
+ *        w_edge[e,h] = m a, ds_edge[e,h] = a (m dout_i.Wh_j - D_i) dz/ds, d_el[i,h] = sum_e ds
  *        (del_part [n_seg, heads] workspace for long rows);
  * nodes: over the transposed CSR (rowptr_t, src_t = source row, eid_t = CSR edge id)
- *        with its own plan: dwh[j] = sum_e w_edge[e,h] dout_i + der_j a_dst + del_j a_src,
+ *        with its own plan: dwh[j] = sum_e w_edge[e,h] dout_i + der_j a_dst + d_el_j a_src,
  *        der[j,h] = sum_e ds_edge[e,h] (part [n_seg_t, heads*fh + heads] workspace);
  *        any head count (der is reduced 8 heads per pass inside the kernel).
  * The dropout mask is recomputed from (dropout_seed, edge, head) exactly as the forward drew it.
@@ -704,7 +704,7 @@ int gnn_gat_backward_edges_f32(const int64_t* rowptr, const int32_t* col, int64_
                                const float* el, const float* er, const float* lse,
                                const float* dout, const float* D, float negative_slope,
                                int32_t mode, float dropout_p, uint64_t dropout_seed,
-                               float* w_edge, float* ds_edge, float* del, int64_t seg_len,
+                               float* w_edge, float* ds_edge, float* d_el, int64_t seg_len,
                                const int32_t* seg_row, const int64_t* seg_begin, int64_t n_seg,
                                const int32_t* long_row, const int32_t* long_seg_ptr,
                                int64_t n_long, const int32_t* rows, int64_t n_rows_list,
@@ -712,7 +712,7 @@ int gnn_gat_backward_edges_f32(const int64_t* rowptr, const int32_t* col, int64_
 int gnn_gat_backward_nodes_f32(const int64_t* rowptr_t, const int32_t* src_t,
                                const int64_t* eid_t, int64_t n_nodes, int64_t heads, int64_t fh,
                                const float* dout, const float* w_edge, const float* ds_edge,
-                               const float* del, const float* a_src, const float* a_dst,
+                               const float* d_el, const float* a_src, const float* a_dst,
                                float* dwh, float* der, int64_t seg_len, const int32_t* seg_row,
                                const int64_t* seg_begin, int64_t n_seg, const int32_t* long_row,
                                const int32_t* long_seg_ptr, int64_t n_long, const int32_t* rows,
@@ -720,7 +720,7 @@ int gnn_gat_backward_nodes_f32(const int64_t* rowptr_t, const int32_t* src_t,
 /*
  * GAT backward, two passes with recomputation (what ops.gat_backward runs; the three passes
  * above remain for the shapes these refuse with GNN_E_UNSUPPORTED):
- * rows : over CSR rows, the prep fused in: dout (as prep), del (as edges), and per row
+ * rows : over CSR rows, the prep fused in: dout (as prep), d_el (as edges), and per row
  *        nstat[i][h] = {el_ih, lse_ih, D_ih, 0} ([n, heads, 4], 16-B aligned); no per-edge
  *        output. Rows: plan segments + `rows` (one wave each) + `short_rows` (8 per wave; the
  *        low-degree rows), every row exactly once. a_dst (nullable, [heads * fh]): er_j
@@ -738,7 +738,7 @@ int gnn_gat_backward_rows_f32(const int64_t* rowptr, const int32_t* col, int64_t
                               const float* el, const float* er, const float* lse, const float* dy,
                               const float* y, int64_t ldo, int32_t elu, float negative_slope,
                               int32_t mode, float dropout_p, uint64_t dropout_seed, float* dout,
-                              float* nstat, float* del, int64_t seg_len, const int32_t* seg_row,
+                              float* nstat, float* d_el, int64_t seg_len, const int32_t* seg_row,
                               const int64_t* seg_begin, int64_t n_seg, const int32_t* long_row,
                               const int32_t* long_seg_ptr, int64_t n_long, const int32_t* rows,
                               int64_t n_rows_list, const int32_t* short_rows, int64_t n_short,
@@ -755,7 +755,7 @@ int gnn_gat_backward_rows_ex_f32(const int64_t* rowptr, const int32_t* col, int6
                                  const float* el, const float* er, const float* lse,
                                  const float* dy, const float* y, int64_t ldo, int32_t elu,
                                  float negative_slope, int32_t mode, float dropout_p,
-                                 uint64_t dropout_seed, float* dout, float* nstat, float* del,
+                                 uint64_t dropout_seed, float* dout, float* nstat, float* d_el,
                                  int64_t seg_len, const int32_t* seg_row, const int64_t* seg_begin,
                                  int64_t n_seg, const int32_t* long_row,
                                  const int32_t* long_seg_ptr, int64_t n_long, const int32_t* rows,
@@ -765,7 +765,7 @@ int gnn_gat_backward_rows_ex_f32(const int64_t* rowptr, const int32_t* col, int6
 int gnn_gat_backward_nodes_recompute_f32(
     const int64_t* rowptr_t, const int32_t* src_t, const int64_t* eid_t, int64_t n_nodes,
     int64_t heads, int64_t fh, const float* dout, const float* nstat, const float* wh,
-    int64_t ldw, const float* er, const float* del, const float* a_src, const float* a_dst,
+    int64_t ldw, const float* er, const float* d_el, const float* a_src, const float* a_dst,
     float negative_slope, int32_t mode, float dropout_p, uint64_t dropout_seed, float* dwh,
     float* der, int64_t seg_len, const int32_t* seg_row, const int64_t* seg_begin, int64_t n_seg,
     const int32_t* long_row, const int32_t* long_seg_ptr, int64_t n_long, const int32_t* rows,

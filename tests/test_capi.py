@@ -35,7 +35,7 @@ def test_exports_are_c_abi():
     out = subprocess.run(["nm", "-D", "--defined-only", str(_lib.library_path())],
                          capture_output=True, text=True, check=True).stdout
     exported = set(re.findall(r"\bT (gnn_\w+)", out))
-    assert set(header_functions()) <= exported
+    assert set(header_functions()) == exported
 
 
 def test_error_strings_and_version(lib):

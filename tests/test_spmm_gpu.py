@@ -589,7 +589,6 @@ def test_packed_tasks_c_abi_contract(dev):
     covered."""
     from graphneuralnetwork_amd import _lib
     from graphneuralnetwork_amd.graph import CsrGraph
-    lib = _lib.load()
     n = 64
     rowptr = torch.arange(n + 1, dtype=torch.int64, device=dev)
     col = torch.arange(n, dtype=torch.int32, device=dev)
@@ -602,9 +601,10 @@ def test_packed_tasks_c_abi_contract(dev):
                                 (8, 0, 0, 0), (4, 0, 0, 0)):
         X = torch.randn(n, F + 4, device=dev)[:, off:off + F]
         y = torch.empty(n, F, device=dev)
-        rc = lib.gnn_spmm_csr_tasks_f32(rowptr.data_ptr(), col.data_ptr(), val.data_ptr(), n,
-                                        X.data_ptr(), X.stride(0), None, 0, F, None, y.data_ptr(),
-                                        F, tp.seg_len, *tp.args(), None, flags, s)
+        rc = _lib.invoke("gnn_spmm_csr_tasks_f32", rowptr=rowptr.data_ptr(), col=col.data_ptr(),
+                         val=val.data_ptr(), n_rows=n, x=X.data_ptr(), ldx=X.stride(0), xh=None,
+                         ldh=0, feat=F, bias=None, y=y.data_ptr(), ldy=F, **tp.segments(),
+                         **tp.task_rows(), partial=None, flags=flags, stream=s)
         assert rc == want, (F, off, flags, rc)
         if rc == 0:
             torch.testing.assert_close(y, X)
