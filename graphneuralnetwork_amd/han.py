@@ -14,21 +14,36 @@ adjacency tensor and cached), instead of the reference's N x N x 2F
 graphs are interleaved into ONE block-diagonal CSR (row n*M + m = node n in
 metapath m), so all metapaths x heads take one GEMM and one aggregation launch,
 and the result is already the [N, M, H*F] stack the semantic attention reads.
-The semantic attention over the M metapath embeddings is a few small dense ops
-and stays in PyTorch.
+The semantic attention over the M metapath embeddings (HAN/models/SemanticAttention.py:15-20)
+runs in the kernels of csrc/han_semantic.hip: the scores ``w2 . tanh(W1 z + b1)`` on the
+matrix cores with the [N M, 128] intermediate kept in registers, the softmax over the M means
+on the device, one pass for the weighted sum, and a device adjoint that recomputes the tanh
+(``_SemanticFn``). CPU tensors, other dtypes, unsupported shapes, fewer than
+``SEMANTIC_MIN_ROWS`` rows N M and a ``project`` that is not the reference's (or carries hooks)
+run the reference's PyTorch expression.
 """
 from __future__ import annotations
 
 import torch
 import torch.nn.functional as F
 from torch import nn
+from torch.autograd.function import once_differentiable
 
 from .gat import GATBase, GraphAttentionLayer, _project
 from .graph import as_csr, from_coo
-from .ops import GAT_DENSE, gat_aggregate, gat_logits
+from .ops import (GAT_DENSE, gat_aggregate, gat_logits, han_semantic_backward,
+                  han_semantic_forward, han_semantic_supported)
 
 # one aggregation launch for all metapaths at inference (HANLayer._batched)
 BATCH_METAPATHS = True
+# the semantic attention in the kernels of csrc/han_semantic.hip (SemanticAttention.forward);
+# SEMANTIC_MIN_ROWS: the smallest N * M that takes them (None: every size). Measured against the
+# torch lines in one process (tools/han_semantic_ab.py, DESIGN.md 5.16), M = 3: from 100K nodes
+# the kernels are 3-5x faster with block ranges apart; at 32 and 3,025 nodes, where both sides
+# are bound by the host, 2x faster by the medians, but single slow blocks reach into torch's
+# range, so those sizes keep torch's lines
+SEMANTIC_FUSED = True
+SEMANTIC_MIN_ROWS = 300_000
 
 
 class GATConv(GATBase):
@@ -59,15 +74,65 @@ class GATConv(GATBase):
         return F.elu(x)
 
 
+class _SemanticFn(torch.autograd.Function):
+    """out = (softmax(project(z).mean(0)) * z).sum(1) on the device (ops.han_semantic_forward)
+    with its adjoint (ops.han_semantic_backward): saves z, the parameters and beta, recomputes
+    the tanh in the backward; once-differentiable."""
+
+    @staticmethod
+    def forward(ctx, z, w1, b1, w2):
+        out, beta = han_semantic_forward(z, w1, b1, w2)
+        ctx.save_for_backward(z, w1, b1, w2, beta)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        z, w1, b1, w2, beta = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dz, dw1, db1, dw2 = han_semantic_backward(g, z, w1, b1, w2, beta, need_dz=need[0],
+                                                  need_params=any(need[1:]))
+        return (dz, dw1 if need[1] else None, db1 if need[2] else None,
+                dw2.view_as(w2) if need[3] else None)
+
+
+def _hooked(m: nn.Module) -> bool:
+    return bool(m._forward_hooks or m._forward_pre_hooks)
+
+
 class SemanticAttention(nn.Module):
-    """HAN/models/SemanticAttention.py:5-20 (metapath-level attention)."""
+    """HAN/models/SemanticAttention.py:5-20 (metapath-level attention). An fp32 device ``z`` of
+    a supported shape with at least ``SEMANTIC_MIN_ROWS`` rows N M runs in the kernels of
+    csrc/han_semantic.hip (``SEMANTIC_FUSED``) when ``project`` is the reference's
+    Linear -> Tanh -> Linear(bias=False) without hooks; everything else runs the reference's two
+    lines."""
 
     def __init__(self, in_size, hidden_size=128):
         super().__init__()
         self.project = nn.Sequential(nn.Linear(in_size, hidden_size), nn.Tanh(),
                                      nn.Linear(hidden_size, 1, bias=False))
 
+    def _fused_ok(self, z) -> bool:
+        if not (SEMANTIC_FUSED and torch.is_tensor(z) and z.is_cuda and z.dtype == torch.float32
+                and z.dim() == 3 and z.shape[0] > 0 and type(self.project) is nn.Sequential
+                and len(self.project) == 3 and not _hooked(self.project)):
+            return False
+        if SEMANTIC_MIN_ROWS is not None and z.shape[0] * z.shape[1] < SEMANTIC_MIN_ROWS:
+            return False
+        l1, act, l2 = self.project
+        if not (type(l1) is nn.Linear and type(act) is nn.Tanh and type(l2) is nn.Linear
+                and l1.bias is not None and l2.bias is None and l2.out_features == 1
+                and l2.in_features == l1.out_features and l1.in_features == z.shape[2]
+                and not any(_hooked(m) for m in (l1, act, l2))
+                and all(p.dtype == torch.float32 and p.device == z.device
+                        for p in (l1.weight, l1.bias, l2.weight))):
+            return False
+        return han_semantic_supported(z.shape[2], l1.out_features, z.shape[1])
+
     def forward(self, z):
+        if self._fused_ok(z):
+            l1, _, l2 = self.project
+            return _SemanticFn.apply(z, l1.weight, l1.bias, l2.weight)
         beta = torch.softmax(self.project(z).mean(0), dim=0)      # (M, 1)
         return (beta.unsqueeze(0) * z).sum(1)                      # (N, D * K)
 

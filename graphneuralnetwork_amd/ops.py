@@ -2378,6 +2378,146 @@ def sup_head_backward(z: torch.Tensor, labels: torch.Tensor, count: torch.Tensor
     return dz
 
 
+def han_semantic_supported(D: int, S: int, M: int) -> bool:
+    """Whether the semantic-attention kernels take z [N, M, D] with a hidden width S
+    (gnn_han_semantic_supported, the one source of the set)."""
+    return bool(_lib.load().gnn_han_semantic_supported(int(D), int(S), int(M)))
+
+
+def _han_rows(t: torch.Tensor, name: str) -> torch.Tensor:
+    """A float32 [N, M, D] (or [N, D]) tensor as the kernels read it: unit stride along D,
+    16-B aligned rows, pitches that are multiples of 4 floats and do not overlap; anything else
+    is copied."""
+    if t.dtype != torch.float32:
+        raise TypeError(f"{name} must be float32 (got {t.dtype})")
+    D = t.shape[-1]
+    st = t.stride()
+    ok = st[-1] == 1 and t.data_ptr() % 16 == 0 and all(s % 4 == 0 for s in st[:-1])
+    if ok and t.dim() == 3:
+        ok = (t.shape[1] <= 1 or st[1] >= D) and \
+            (t.shape[0] <= 1 or st[0] >= t.shape[1] * max(st[1], D))
+    elif ok:
+        ok = t.shape[0] <= 1 or st[0] >= D
+    return t if ok else t.contiguous()
+
+
+def _han_pitches(t: torch.Tensor) -> tuple[int, int]:
+    """(ld_n, ld_m) of a [N, M, D] tensor from ``_han_rows`` (a size-1 axis has no pitch of its
+    own)."""
+    N, M, D = t.shape
+    ld_m = t.stride(1) if M > 1 else D
+    ld_n = t.stride(0) if N > 1 else M * ld_m
+    return ld_n, ld_m
+
+
+def _han_operands(z, w1, b1, w2):
+    _require_device(z, w1, b1, w2)
+    if z.dim() != 3:
+        raise ValueError(f"z must be [N, M, D] (got {tuple(z.shape)})")
+    N, M, D = z.shape
+    S = w1.shape[0] if w1.dim() == 2 else -1
+    if w1.shape != (S, D) or b1.shape != (S,) or w2.numel() != S:
+        raise ValueError(f"project must be Linear({D}, S) -> Tanh -> Linear(S, 1): got weights "
+                         f"{tuple(w1.shape)}, {tuple(b1.shape)}, {tuple(w2.shape)}")
+    for name, t in (("w1", w1), ("b1", b1), ("w2", w2)):
+        if t.dtype != torch.float32:
+            raise TypeError(f"{name} must be float32 (got {t.dtype})")
+    if not han_semantic_supported(D, S, M):
+        raise ValueError(f"semantic attention kernels do not take D={D}, S={S}, M={M} "
+                         "(han_semantic_supported)")
+    return (_han_rows(z, "z"), w1.contiguous(), b1.contiguous(), w2.reshape(-1).contiguous(),
+            N, M, D, S)
+
+
+def _han_workspace(lib, N, M, D, S, dev) -> torch.Tensor:
+    return torch.empty(int(lib.gnn_han_semantic_workspace_bytes(N, M, D, S)), dtype=torch.uint8,
+                       device=dev)
+
+
+def han_semantic_forward(z: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor,
+                         w2: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """HAN's semantic attention (HAN/models/SemanticAttention.py:15-20) over z [N, M, D] with
+    ``project = Linear(D, S) -> Tanh -> Linear(S, 1, bias=False)`` given as w1 [S, D], b1 [S],
+    w2 [1, S] or [S] (gnn_han_semantic_fwd_f32): (out [N, D], beta [M]) with
+    ``beta = softmax(project(z).mean(0))`` and ``out = (beta * z).sum(1)``. The scores run on
+    the matrix cores with the [N M, S] intermediate kept in registers; beta stays on the
+    device. A pitched z (unit stride along D, 16-B aligned rows) is read in place."""
+    z, w1, b1, w2, N, M, D, S = _han_operands(z, w1, b1, w2)
+    lib = _lib.load()
+    dev = z.device
+    out = torch.empty((N, D), dtype=torch.float32, device=dev)
+    beta = torch.empty(M, dtype=torch.float32, device=dev)
+    if N == 0:  # the mean of nothing
+        return out, beta.fill_(float("nan"))
+    ld_n, ld_m = _han_pitches(z)
+    ws = _han_workspace(lib, N, M, D, S, dev)
+    _lib.run("gnn_han_semantic_fwd_f32", z=z.data_ptr(), ld_n=ld_n, ld_m=ld_m, N=N, M=M, D=D,
+             S=S, w1=w1.data_ptr(), b1=b1.data_ptr(), w2=w2.data_ptr(), w=None,
+             beta=beta.data_ptr(), out=out.data_ptr(), ldo=D, ws=ws.data_ptr(),
+             ws_bytes=ws.numel(), stream=_lib.stream_handle(dev))
+    return out, beta
+
+
+def han_semantic_backward(g: torch.Tensor, z: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor,
+                          w2: torch.Tensor, beta: torch.Tensor, need_dz: bool = True,
+                          need_params: bool = True, dz_out: torch.Tensor | None = None):
+    """The adjoint of ``han_semantic_forward`` (gnn_han_semantic_bwd_f32) for g = d out [N, D]
+    and the forward's beta: (dz [N, M, D], dw1 [S, D], db1 [S], dw2 [S]); ``need_dz`` False
+    skips the input-side pass (dz None), ``need_params`` False the parameter-side pass (the
+    three None). tanh(W1 z + b1) is recomputed on the matrix cores; no [N M, S] tensor, no float
+    atomics, bit-identical from run to run. ``dz_out``: a float32 [N, M, D] tensor the kernels
+    can write (``_han_rows`` layout) instead of a new one."""
+    _require_device(g, beta, dz_out)
+    z, w1, b1, w2, N, M, D, S = _han_operands(z, w1, b1, w2)
+    if g.shape != (N, D):
+        raise ValueError(f"g must be [{N}, {D}] (got {tuple(g.shape)})")
+    if beta.dtype != torch.float32 or beta.shape != (M,) or not beta.is_contiguous():
+        raise ValueError(f"beta must be a contiguous float32 [{M}] tensor")
+    lib = _lib.load()
+    dev = z.device
+    g = _han_rows(g, "g")
+    dz = None
+    if need_dz:
+        dz = dz_out if dz_out is not None else torch.empty((N, M, D), dtype=torch.float32,
+                                                           device=dev)
+        if dz.shape != (N, M, D) or _han_rows(dz, "dz_out") is not dz:
+            raise ValueError(f"dz_out must be a float32 [{N}, {M}, {D}] tensor with unit stride "
+                             "along D and 16-B aligned rows")
+    dw1 = db1 = dw2 = None
+    if need_params:
+        dw1 = torch.empty((S, D), dtype=torch.float32, device=dev)
+        db1 = torch.empty(S, dtype=torch.float32, device=dev)
+        dw2 = torch.empty(S, dtype=torch.float32, device=dev)
+        if N == 0:
+            dw1.zero_(), db1.zero_(), dw2.zero_()
+    if N == 0 or not (need_dz or need_params):
+        return dz, dw1, db1, dw2
+    ld_n, ld_m = _han_pitches(z)
+    ldd_n, ldd_m = _han_pitches(dz) if dz is not None else (M * D, D)
+    ws = _han_workspace(lib, N, M, D, S, dev)
+    _lib.run("gnn_han_semantic_bwd_f32", g=g.data_ptr(), ldg=g.stride(0) if N > 1 else D,
+             z=z.data_ptr(), ld_n=ld_n, ld_m=ld_m, N=N, M=M, D=D, S=S, w1=w1.data_ptr(),
+             b1=b1.data_ptr(), w2=w2.data_ptr(), beta=beta.data_ptr(), dz=_lib.ptr(dz),
+             lddz_n=ldd_n, lddz_m=ldd_m, dw1=_lib.ptr(dw1), db1=_lib.ptr(db1),
+             dw2=_lib.ptr(dw2), ws=ws.data_ptr(), ws_bytes=ws.numel(),
+             stream=_lib.stream_handle(dev))
+    return dz, dw1, db1, dw2
+
+
+def han_tanh(x: torch.Tensor) -> torch.Tensor:
+    """The semantic-attention kernels' tanh of a float32 tensor (gnn_han_tanh_f32): what the
+    tests measure against float64."""
+    _require_device(x)
+    if x.dtype != torch.float32:
+        raise TypeError(f"x must be float32 (got {x.dtype})")
+    x = x.contiguous()
+    y = torch.empty_like(x)
+    if x.numel():
+        _lib.run("gnn_han_tanh_f32", x=x.data_ptr(), y=y.data_ptr(), n=x.numel(),
+                 stream=_lib.stream_handle(x.device))
+    return y
+
+
 # The fused layer is opt-in (set SAGE_FUSED_MIN_ROWS to the smallest frontier to fuse): at
 # cfg4 it gains 2-3 % on layer 0 (62,479 rows: 110 vs 112 us) and loses on the 8,192-row
 # layer 1 (33 vs 25 us) -- its gathers and MFMAs do not overlap, so it costs about their

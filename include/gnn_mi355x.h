@@ -1354,6 +1354,50 @@ int gnn_sup_head_bwd_f32(const float* z, int64_t ldz, const int64_t* labels,
                          const float* upstream, const double* inv_valid,
                          const uint32_t* status, float* dz, int64_t lddz, void* stream);
 
+/* ---- HAN's semantic (metapath-level) attention (han_semantic.hip) ----
+ * HAN/models/SemanticAttention.py:15-20: for z [N, M, D] (D = heads x hidden),
+ *   w = project(z).mean(0), project = Linear(D, S) -> Tanh -> Linear(S, 1, bias=False);
+ *   beta = softmax(w, dim=0); out = (beta * z).sum(1),
+ * and its adjoint. z[n, m, :] lives at z + n ld_n + m ld_m (fp32, unit stride along D, 16-B
+ * aligned rows: ld_m >= D, ld_n >= M ld_m, both multiples of 4), so a pitched view works without
+ * a copy; row offsets are 64-bit. w1 [S, D] contiguous (nn.Linear's [out, in]), b1 [S], w2 [S].
+ * The rows n M + m go through v_mfma_f32_16x16x4_f32 in tiles of 64 on a persistent grid with
+ * W1 resident; nothing of size [N M, S] is written. tanh(x) = 1 - 2 / (1 + exp(2x)) on the
+ * hardware exponential and reciprocal (saturates to +-1 without a clamp, NaN stays NaN). Every
+ * sum runs in an order fixed by the shapes (no floating-point atomics): bit-identical from run
+ * to run. Nothing is read back on the host.
+ *   gnn_han_semantic_supported(D, S, M): 1 for D in {16, 32, 64, 128}, S = 128, 1 <= M <= 8.
+ *   gnn_han_semantic_workspace_bytes(N, M, D, S): bytes of the 8-B aligned device workspace of
+ *     either call; grows with N only up to the persistent grids' cap.
+ *   gnn_han_semantic_fwd_f32: w [M] (nullable) and beta [M] (fp32, device) and out [N, D]
+ *     (pitch ldo >= D, 16-B aligned rows): one pass for the scores with one double partial per
+ *     (workgroup, m), one wavefront that adds them in workgroup order and takes the softmax
+ *     with the maximum subtracted, one pass out[n] = sum_m beta[m] z[n, m] (m ascending).
+ *   gnn_han_semantic_bwd_f32: given g = d out [N, D] (pitch ldg) and the forward's beta:
+ *     dbeta[m] = sum_n g[n] . z[n, m]; dw[m] = beta[m] (dbeta[m] - sum_k beta[k] dbeta[k]);
+ *     with t = tanh(W1 z_r + b1) recomputed and q_r = dw[m] / N w2 (1 - t^2):
+ *     dz[n, m] = beta[m] g[n] + q_r W1 (pitches lddz_n, lddz_m as z's), dw1 [S, D] = sum_r
+ *     q_r^T z_r, db1 [S] = sum_r q_r, dw2 [S] = sum_r dw[m] / N t_r. Any of dz, dw1, db1, dw2
+ *     may be NULL: dz NULL skips the input-side pass, all three of dw1, db1, dw2 NULL the
+ *     parameter-side pass.
+ *   gnn_han_tanh_f32: y[i] = the kernels' tanh of x[i], for measuring it.
+ * Rejected before any launch: null operands, negative sizes, a pitch below the width, a short
+ * workspace (GNN_E_ARG), misaligned pointers or pitches (GNN_E_ALIGN), shapes outside
+ * gnn_han_semantic_supported (GNN_E_UNSUPPORTED). N = 0 returns GNN_OK with nothing launched. */
+int gnn_han_semantic_supported(int64_t D, int64_t S, int64_t M);
+int64_t gnn_han_semantic_workspace_bytes(int64_t N, int64_t M, int64_t D, int64_t S);
+int gnn_han_semantic_fwd_f32(const float* z, int64_t ld_n, int64_t ld_m, int64_t N, int64_t M,
+                             int64_t D, int64_t S, const float* w1, const float* b1,
+                             const float* w2, float* w, float* beta, float* out, int64_t ldo,
+                             void* ws, int64_t ws_bytes, void* stream);
+int gnn_han_semantic_bwd_f32(const float* g, int64_t ldg, const float* z, int64_t ld_n,
+                             int64_t ld_m, int64_t N, int64_t M, int64_t D, int64_t S,
+                             const float* w1, const float* b1, const float* w2,
+                             const float* beta, float* dz, int64_t lddz_n, int64_t lddz_m,
+                             float* dw1, float* db1, float* dw2, void* ws, int64_t ws_bytes,
+                             void* stream);
+int gnn_han_tanh_f32(const float* x, float* y, int64_t n, void* stream);
+
 /*
  * Edge-cut halo exchange (SURVEY 8(b) gnn_halo_alltoallv; the all-to-all-v that
  * distributed.EdgeCutSpmm / EdgeCutGat run through torch.distributed on the nccl = RCCL
