@@ -1,0 +1,203 @@
+"""Metapath graphs of a heterogeneous graph, built on the device.
+
+The reference's HAN loader turns a relation (paper x author, paper x field) into a metapath
+graph on the host (``HeteroGraph.get_mate_path_graph``, HAN/utils/data_utils.py:85-89):
+
+    mate_path_adj = HGraphs[key] * HGraphs[key].T     # scipy sparse product
+    mate_path_adj[mate_path_adj > 0] = 1
+    return mate_path_adj.toarray()                    # dense N x N
+
+Here the same structure is a boolean sparse x sparse product written straight into a
+``CsrGraph`` (csrc/relation_product.hip: ``gnn_relation_product_count`` / ``_fill``), which
+``han.GATConv`` / ``HANLayer`` take as they take the dense array: row i holds the set union
+of the B-rows named by row i of A, ascending, without duplicates -- the edge order
+``graph.from_dense(reference_output, "positive")`` gives. No dense N x N array and nothing
+sized by the number of partial products exists at any point.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import torch
+
+from . import _lib
+from .graph import CsrGraph, from_coo, from_torch_sparse
+
+
+def _operand(x, device=None) -> CsrGraph:
+    """A relation operand as a CsrGraph: a CsrGraph, a torch sparse COO / CSR tensor (every
+    stored entry an edge) or a ``(row, col, (n_rows, n_cols))`` triple."""
+    if isinstance(x, CsrGraph):
+        g = x
+    elif isinstance(x, torch.Tensor):
+        if x.layout == torch.strided:
+            raise TypeError("a relation is sparse: pass a torch sparse tensor, a CsrGraph or a "
+                            "(row, col, shape) triple")
+        g = from_torch_sparse(x, "all")
+    elif isinstance(x, (tuple, list)) and len(x) == 3:
+        row, col, shape = x
+        row = torch.as_tensor(row, dtype=torch.int64)
+        col = torch.as_tensor(col, dtype=torch.int64, device=row.device)
+        if row.shape != col.shape or row.dim() != 1:
+            raise ValueError("row and col must be 1-D and of the same length")
+        n_rows, n_cols = (int(v) for v in shape)
+        if row.numel() and (int(row.min()) < 0 or int(row.max()) >= n_rows):
+            raise IndexError("relation row index out of range")
+        g = from_coo(row, col, torch.ones(row.numel(), device=row.device), n_rows, n_cols,
+                     check=False)  # the product checks the column ids
+    else:
+        raise TypeError("a relation operand is a CsrGraph, a torch sparse tensor or a "
+                        "(row, col, shape) triple")
+    return g if device is None else g.to(device)
+
+
+def class_limits() -> tuple[int, int]:
+    """(short_max, mid_max): the largest row upper bound ub = sum of the named B-rows' lengths
+    built by one wavefront in registers, and the largest built in an LDS table; rows above
+    are built in a bitmap (gnn_relation_product_class_limits)."""
+    s, m = ctypes.c_int64(0), ctypes.c_int64(0)
+    _lib.check(_lib.load().gnn_relation_product_class_limits(ctypes.byref(s), ctypes.byref(m)),
+               "gnn_relation_product_class_limits")
+    return int(s.value), int(m.value)
+
+
+def relation_product(a, b) -> CsrGraph:
+    """C = (A . B) > 0 as a CsrGraph with unit values: A [n, k], B [k, m]. Device operands run
+    the HIP kernels; CPU operands run ``relation_product_torch``."""
+    a = _operand(a)
+    b = _operand(b, a.device)
+    if a.n_cols != b.n_rows:
+        raise ValueError(f"shapes do not chain: A is [{a.n_rows}, {a.n_cols}], "
+                         f"B is [{b.n_rows}, {b.n_cols}]")
+    if not a.rowptr.is_cuda:
+        return relation_product_torch(a, b)
+    dev = a.device
+    n, k, m = a.n_rows, a.n_cols, b.n_cols
+    lib = _lib.load()
+    nbytes = int(lib.gnn_relation_product_workspace_bytes(n, k, m, a.nnz, b.nnz))
+    if nbytes < 0:
+        _lib.check(nbytes, "gnn_relation_product_workspace_bytes")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    rowptr = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    nnz = ctypes.c_int64(0)
+    stream = _lib.stream_handle(dev)
+    operands = dict(a_rowptr=a.rowptr.data_ptr(), a_col=_lib.ptr(a.col) if a.nnz else None,
+                    nnz_a=a.nnz, b_rowptr=b.rowptr.data_ptr(),
+                    b_col=_lib.ptr(b.col) if b.nnz else None, nnz_b=b.nnz, n=n, k=k, m=m,
+                    workspace=ws.data_ptr(), workspace_bytes=nbytes, stream=stream)
+    rc = _lib.invoke("gnn_relation_product_count", c_rowptr=rowptr.data_ptr(),
+                     nnz_out=ctypes.addressof(nnz), **operands)
+    if rc == _lib.E_ARG:
+        raise IndexError("relation column id out of range (or a malformed rowptr)")
+    _lib.check(rc, "gnn_relation_product_count")
+    col = torch.empty(int(nnz.value), dtype=torch.int32, device=dev)
+    _lib.run("gnn_relation_product_fill", c_rowptr=rowptr.data_ptr(),
+             c_col=col.data_ptr() if col.numel() else None, nnz_c=col.numel(), **operands)
+    return CsrGraph(rowptr, col, torch.ones(col.numel(), dtype=torch.float32, device=dev), n, m)
+
+
+def relation_product_torch(a, b) -> CsrGraph:
+    """``relation_product`` restated in torch ops (any device): every partial product expanded,
+    key = row * m + col, ``torch.unique``. The CPU path and the oracle of the kernels; its
+    memory grows with the number of partial products, which the kernels' does not."""
+    a = _operand(a)
+    b = _operand(b, a.device)
+    if a.n_cols != b.n_rows:
+        raise ValueError(f"shapes do not chain: A is [{a.n_rows}, {a.n_cols}], "
+                         f"B is [{b.n_rows}, {b.n_cols}]")
+    dev = a.device
+    n, k, m = a.n_rows, a.n_cols, b.n_cols
+    ac, bc = a.col.to(torch.int64), b.col.to(torch.int64)
+    if (ac.numel() and (int(ac.min()) < 0 or int(ac.max()) >= k)) or \
+            (bc.numel() and (int(bc.min()) < 0 or int(bc.max()) >= m)):
+        raise IndexError("relation column id out of range")
+    a_row = torch.repeat_interleave(torch.arange(n, device=dev, dtype=torch.int64),
+                                    a.rowptr[1:] - a.rowptr[:-1])
+    deg = (b.rowptr[1:] - b.rowptr[:-1])[ac]           # products of each entry of A
+    first = torch.cumsum(deg, 0) - deg
+    total = int(deg.sum()) if deg.numel() else 0
+    src = torch.repeat_interleave(b.rowptr[:-1][ac] - first, deg) + \
+        torch.arange(total, device=dev, dtype=torch.int64)
+    key = torch.unique(torch.repeat_interleave(a_row, deg) * m + bc[src])
+    rowptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    if key.numel():
+        torch.cumsum(torch.bincount(key // m, minlength=n), 0, out=rowptr[1:])
+    col = (key % m).to(torch.int32).contiguous() if key.numel() else \
+        torch.zeros(0, dtype=torch.int32, device=dev)
+    return CsrGraph(rowptr, col, torch.ones(col.numel(), dtype=torch.float32, device=dev), n, m)
+
+
+def metapath_graph(b) -> CsrGraph:
+    """The metapath graph of a relation B [n, k]: (B . B^T) > 0, [n, n], symmetric. B^T is
+    built on the operand's device (``CsrGraph.transpose``)."""
+    b = _operand(b)
+    bt = b.transpose()
+    if bt is b:  # a square relation marked symmetric is its own transpose
+        bt = CsrGraph(b.rowptr, b.col, b.val, b.n_rows, b.n_cols)
+    g = relation_product(b, bt)
+    g.symmetric = True
+    return g
+
+
+def _positive_entries(rel, device) -> CsrGraph:
+    """The entries > 0 of a valued relation as a CsrGraph on ``device`` (None: the operand's
+    own device; scipy matrices go to the ROCm device when there is one). A negative entry
+    raises: under the reference's ``adj[adj > 0] = 1`` it would leave non-unit values behind,
+    and this builder carries no values."""
+    if isinstance(rel, CsrGraph):
+        row = torch.repeat_interleave(
+            torch.arange(rel.n_rows, device=rel.device, dtype=torch.int64),
+            rel.rowptr[1:] - rel.rowptr[:-1])
+        col, val, shape = rel.col.to(torch.int64), rel.val, (rel.n_rows, rel.n_cols)
+    elif isinstance(rel, torch.Tensor):
+        if rel.layout == torch.strided:
+            if rel.dim() != 2:
+                raise TypeError("a relation is a 2-D matrix")
+            idx = (rel != 0).nonzero()
+            row, col, val, shape = idx[:, 0], idx[:, 1], rel[rel != 0], tuple(rel.shape)
+        else:
+            coo = rel.to_sparse_coo() if rel.layout != torch.sparse_coo else rel
+            row, col = coo._indices()[0], coo._indices()[1]
+            val, shape = coo._values(), tuple(rel.shape)
+    elif hasattr(rel, "tocoo"):  # a scipy sparse matrix: never imported here, only recognised
+        coo = rel.tocoo()
+        row = torch.from_numpy(coo.row.astype("int64"))
+        col = torch.from_numpy(coo.col.astype("int64"))
+        val = torch.from_numpy(coo.data.astype("float64"))
+        shape = tuple(int(v) for v in coo.shape)
+        if device is None and torch.cuda.is_available():
+            device = "cuda"
+    else:
+        raise TypeError("a relation is a scipy sparse matrix, a torch tensor or a CsrGraph")
+    if val.numel() and bool((val < 0).any()):
+        raise ValueError("a relation with negative entries has no metapath graph here: the "
+                         "reference's adj[adj > 0] = 1 would keep non-unit values")
+    keep = val > 0
+    row, col = row[keep], col[keep]
+    if device is not None:
+        row, col = row.to(device), col.to(device)
+    return from_coo(row, col, torch.ones(row.numel(), device=row.device), shape[0], shape[1])
+
+
+class HeteroGraph:
+    """The reference's ``HeteroGraph`` (HAN/utils/data_utils.py:74-89) over the device builder:
+    same constructor argument, ``__iter__``, ``__len__`` and ``get_mate_path_graph(key)``, but
+    each metapath graph is a ``CsrGraph`` (what ``han.HANLayer`` takes) instead of a dense
+    array. Relations may be scipy sparse matrices (when scipy is installed; it is never
+    imported here), torch sparse or dense tensors, or ``CsrGraph``s; entries > 0 are edges and a
+    negative entry raises ``ValueError``. ``device``: where the graphs are built (default: the
+    relation's own device; the ROCm device for scipy matrices when there is one)."""
+
+    def __init__(self, HGraphs: dict, device=None):
+        self.HGraphs = HGraphs
+        self.device = device
+
+    def __iter__(self):
+        for key in self.HGraphs.keys():
+            yield self.get_mate_path_graph(key)
+
+    def __len__(self):
+        return len(self.HGraphs)
+
+    def get_mate_path_graph(self, mate_path) -> CsrGraph:
+        return metapath_graph(_positive_entries(self.HGraphs[mate_path], self.device))

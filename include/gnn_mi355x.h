@@ -1221,6 +1221,48 @@ int gnn_gcn_adjacency_build(const int64_t* src, const int64_t* dst, int64_t n_ed
 int gnn_gcn_adjacency_fill(const void* workspace, int64_t n_edges, int64_t n_nodes, int64_t nnz,
                            int64_t* rowptr, int32_t* col, float* val, void* stream);
 
+/*
+ * Boolean relation product on the device: C = (A . B) > 0 as structure only -- the metapath
+ * step of the reference's HAN loader (HAN/utils/data_utils.py:85-89, PvsA * PvsA.T then
+ * > 0), written as CSR instead of a dense [n, m] array.
+ *   A [n, k], B [k, m], C [n, m]: CSR, rowptr int64 [rows + 1] (rowptr[0] = 0, ascending,
+ *     rowptr[rows] = nnz), col int32 [nnz]. A's and B's ids may come in any order within a
+ *     row and may repeat; stored values are not read, every stored entry is an edge.
+ *   Order guarantee: row i of C is the SET union of the B-rows named by row i of A, in
+ *     ASCENDING column order without duplicates (the edge order of a dense (A . B) > 0 read
+ *     row-major), so the result is bit-identical from run to run.
+ * Two calls, the library never allocates:
+ *   gnn_relation_product_count: checks every id of A against k and of B against m (an id
+ *     out of range, or a rowptr that is not one -> GNN_E_ARG, and nothing is read through
+ *     it), writes c_rowptr [n + 1] and returns nnz(C) in *nnz_out (host). SYNCHRONISES
+ *     `stream` (twice: after the check and for nnz), as gnn_gcn_adjacency_build does.
+ *   gnn_relation_product_fill: writes c_col [nnz_c] by recomputing each row, exactly
+ *     c_rowptr[i+1] - c_rowptr[i] ids for row i; same operands, c_rowptr and workspace as
+ *     the count call, the workspace untouched in between. Does not synchronise.
+ * Rows are classed by ub[i] = sum over A's row i of the named B-rows' lengths:
+ *   gnn_relation_product_class_limits: *short_max = the largest ub built by one wavefront
+ *     in registers, *mid_max = the largest ub built in an LDS hash table; rows above it
+ *     are built in a bitmap of m bits.
+ * Workspace: gnn_relation_product_workspace_bytes(n, k, m, nnz_a, nnz_b) bytes: O(n) row
+ *   arrays plus a fixed number (<= 256) of m-bit bitmaps. It does NOT grow with the number
+ *   of partial products sum_i ub[i].
+ * Limits: n, k, m < 2^31 - 1 (else GNN_E_UNSUPPORTED, from the workspace query too; a
+ *   negative size -> GNN_E_ARG); nnz(C) may exceed 2^31 (64-bit offsets throughout).
+ */
+int64_t gnn_relation_product_workspace_bytes(int64_t n, int64_t k, int64_t m, int64_t nnz_a,
+                                             int64_t nnz_b);
+int gnn_relation_product_class_limits(int64_t* short_max, int64_t* mid_max);
+int gnn_relation_product_count(const int64_t* a_rowptr, const int32_t* a_col, int64_t nnz_a,
+                               const int64_t* b_rowptr, const int32_t* b_col, int64_t nnz_b,
+                               int64_t n, int64_t k, int64_t m, int64_t* c_rowptr,
+                               int64_t* nnz_out, void* workspace, int64_t workspace_bytes,
+                               void* stream);
+int gnn_relation_product_fill(const int64_t* a_rowptr, const int32_t* a_col, int64_t nnz_a,
+                              const int64_t* b_rowptr, const int32_t* b_col, int64_t nnz_b,
+                              int64_t n, int64_t k, int64_t m, const int64_t* c_rowptr,
+                              int32_t* c_col, int64_t nnz_c, void* workspace,
+                              int64_t workspace_bytes, void* stream);
+
 /* ---- CPython-exact host sampler (pysample.cpp; host memory, no stream) ----
  * Bit-exact restatement of the reference's host-side GraphSAGE sampling, which draws
  * from CPython's global `random` and iterates Python sets:
