@@ -13,6 +13,12 @@ Here the same structure is a boolean sparse x sparse product written straight in
 of the B-rows named by row i of A, ascending, without duplicates -- the edge order
 ``graph.from_dense(reference_output, "positive")`` gives. No dense N x N array and nothing
 sized by the number of partial products exists at any point.
+
+The loader's mini-batch path slices those dense arrays, ``HG_adj[idx][:, idx]`` once per step and
+metapath (``collect_f.__call__``, HAN/utils/data_utils.py:92-101). Here the slice is the induced
+subgraph of a ``CsrGraph`` written as a ``CsrGraph`` [b, b] (csrc/induced_subgraph.hip:
+``gnn_induced_subgraph_map`` / ``_count`` / ``_fill``; ``induced_subgraphs``), rows ascending by
+position, values carried, and ``collect_f`` is the reference's class over it.
 """
 from __future__ import annotations
 
@@ -201,3 +207,189 @@ class HeteroGraph:
 
     def get_mate_path_graph(self, mate_path) -> CsrGraph:
         return metapath_graph(_positive_entries(self.HGraphs[mate_path], self.device))
+
+
+# ------------------------------------------------------------------ mini-batches: A[idx][:, idx]
+STATUS_BAD_IDX, STATUS_BAD_GRAPH, STATUS_REPEAT = 1, 2, 4   # bits of the kernels' status word
+
+
+def subgraph_class_limits() -> tuple[int, int, int]:
+    """(short_max, mid_max, lds_bits) of the induced-subgraph fill: the largest kept count of a
+    row sorted by one wavefront, the largest sorted in LDS, and the largest batch whose rank
+    bitmap lives in LDS (gnn_induced_subgraph_class_limits)."""
+    s, m, b = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+    _lib.check(_lib.load().gnn_induced_subgraph_class_limits(
+        ctypes.byref(s), ctypes.byref(m), ctypes.byref(b)), "gnn_induced_subgraph_class_limits")
+    return int(s.value), int(m.value), int(b.value)
+
+
+def _batch_index(idx, device) -> torch.Tensor:
+    """A batch as an int64 [b] tensor on ``device``: a 1-D tensor or array, or what a DataLoader
+    over an index array hands a collate_fn (a list of 0-d tensors, numpy integers or ints)."""
+    if isinstance(idx, torch.Tensor):
+        t = idx
+    else:
+        idx = list(idx)
+        if idx and isinstance(idx[0], torch.Tensor):
+            t = torch.stack([torch.as_tensor(v) for v in idx])
+        else:
+            t = torch.tensor([int(v) for v in idx], dtype=torch.int64)
+    if t.dim() != 1:
+        raise ValueError("a batch is a 1-D list of node ids")
+    if t.dtype.is_floating_point or t.dtype == torch.bool:
+        raise TypeError("node ids are integers")
+    return t.to(device=device, dtype=torch.int64).contiguous()
+
+
+def _raise_status(status: int) -> None:
+    if status & STATUS_BAD_IDX:
+        raise IndexError("batch id out of range for the graph")
+    if status & STATUS_BAD_GRAPH:
+        raise IndexError("graph column id out of range (or a malformed rowptr) in a selected row")
+    if status & STATUS_REPEAT:
+        raise ValueError("a selected row repeats a selected column: coalesce the graph first")
+
+
+def _square(gs) -> int:
+    n = gs[0].n_rows
+    for g in gs:
+        if g.n_rows != g.n_cols:
+            raise ValueError(f"an induced subgraph needs a square graph, got [{g.n_rows}, "
+                             f"{g.n_cols}]")
+        if g.n_rows != n:
+            raise ValueError("the graphs of one batch share their node set")
+    return n
+
+
+def induced_subgraph_torch(g: CsrGraph, idx) -> CsrGraph:
+    """``induced_subgraph`` restated in torch ops (any device): the selected rows expanded, each
+    column looked up in the stably sorted ``idx`` with two ``searchsorted`` calls, the runs
+    expanded, and a stable argsort of ``row * b + position``. The CPU path and the oracle of the
+    kernels; its memory grows with the selected rows' full lengths, which the kernels' does not."""
+    n = _square([g])
+    dev = g.device
+    idx = _batch_index(idx, dev)
+    b = idx.numel()
+    if b and (int(idx.min()) < 0 or int(idx.max()) >= n):
+        raise IndexError("batch id out of range for the graph")
+    lo_e, hi_e = g.rowptr[idx], g.rowptr[idx + 1]
+    if b and (int(lo_e.min()) < 0 or int((hi_e - lo_e).min()) < 0 or int(hi_e.max()) > g.nnz):
+        raise IndexError("malformed rowptr in a selected row")
+    deg = hi_e - lo_e
+    total = int(deg.sum()) if b else 0
+    first = torch.cumsum(deg, 0) - deg
+    row = torch.repeat_interleave(torch.arange(b, device=dev, dtype=torch.int64), deg)
+    src = torch.repeat_interleave(lo_e - first, deg) + \
+        torch.arange(total, device=dev, dtype=torch.int64)
+    c = g.col[src].to(torch.int64)
+    if total and (int(c.min()) < 0 or int(c.max()) >= n):
+        raise IndexError("graph column id out of range in a selected row")
+    sorted_idx, perm = torch.sort(idx, stable=True)
+    lo = torch.searchsorted(sorted_idx, c, right=False)
+    run = torch.searchsorted(sorted_idx, c, right=True) - lo   # positions that hold the column
+    kept = int(run.sum()) if total else 0
+    ent = torch.repeat_interleave(torch.arange(total, device=dev, dtype=torch.int64), run)
+    off = torch.arange(kept, device=dev, dtype=torch.int64) - \
+        torch.repeat_interleave(torch.cumsum(run, 0) - run, run)
+    pos = perm[lo[ent] + off] if kept else torch.zeros(0, dtype=torch.int64, device=dev)
+    key = row[ent] * b + pos
+    order = torch.argsort(key, stable=True)
+    key = key[order]
+    if kept > 1 and bool((key[1:] == key[:-1]).any()):
+        raise ValueError("a selected row repeats a selected column: coalesce the graph first")
+    rowptr = torch.zeros(b + 1, dtype=torch.int64, device=dev)
+    if kept:
+        torch.cumsum(torch.bincount(key // b, minlength=b), 0, out=rowptr[1:])
+    out = CsrGraph(rowptr, pos[order].to(torch.int32).contiguous(),
+                   g.val[src[ent][order]].contiguous(), b, b)
+    out.symmetric = g.symmetric
+    return out
+
+
+def induced_subgraphs(gs, idx) -> list[CsrGraph]:
+    """``[A[idx][:, idx] for A in gs]`` as CsrGraphs [b, b], values carried, each row in ascending
+    position order. ``gs``: square CsrGraphs over one node set, on one device; ``idx``: the
+    batch's node ids, in any order, repeats allowed. Device operands run csrc/
+    induced_subgraph.hip: one map of the batch, a count per graph, ONE host read of the totals
+    and the status word, a fill per graph and a second read of the status word (a repeated
+    (row, position) pair shows in the fill). CPU operands run ``induced_subgraph_torch``."""
+    gs = list(gs)
+    if not gs:
+        return []
+    n = _square(gs)
+    dev = gs[0].device
+    if not gs[0].rowptr.is_cuda:
+        return [induced_subgraph_torch(g, idx) for g in gs]
+    idx = _batch_index(idx, dev)
+    b, M = idx.numel(), len(gs)
+    lib = _lib.load()
+    nbytes = int(lib.gnn_induced_subgraph_workspace_bytes(n, b))
+    if nbytes < 0:
+        _lib.check(nbytes, "gnn_induced_subgraph_workspace_bytes")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    stream = _lib.stream_handle(dev)
+    batch = dict(idx=idx.data_ptr() if b else None, b=b, n=n, status=status.data_ptr(),
+                 workspace=ws.data_ptr(), workspace_bytes=nbytes, stream=stream)
+    _lib.run("gnn_induced_subgraph_map", **batch)
+    rowptrs = torch.empty((M, b + 1), dtype=torch.int64, device=dev)
+    for m, g in enumerate(gs):
+        _lib.run("gnn_induced_subgraph_count", rowptr=g.rowptr.data_ptr(),
+                 col=_lib.ptr(g.col) if g.nnz else None, nnz=g.nnz,
+                 c_rowptr=rowptrs[m].data_ptr(), **batch)
+    host = torch.cat([rowptrs[:, b], status.to(torch.int64)]).cpu()  # the one read before the fills
+    _raise_status(int(host[M]))
+    out = []
+    for m, g in enumerate(gs):
+        nnz_c = int(host[m])
+        col = torch.empty(nnz_c, dtype=torch.int32, device=dev)
+        val = torch.empty(nnz_c, dtype=torch.float32, device=dev)
+        _lib.run("gnn_induced_subgraph_fill", rowptr=g.rowptr.data_ptr(),
+                 col=_lib.ptr(g.col) if g.nnz else None, val=_lib.ptr(g.val) if g.nnz else None,
+                 nnz=g.nnz, c_rowptr=rowptrs[m].data_ptr(), c_col=col.data_ptr() if nnz_c else None,
+                 c_val=val.data_ptr() if nnz_c else None, nnz_c=nnz_c, **batch)
+        c = CsrGraph(rowptrs[m], col, val, b, b)
+        c.symmetric = g.symmetric
+        out.append(c)
+    _raise_status(int(status))
+    return out
+
+
+def induced_subgraph(g: CsrGraph, idx) -> CsrGraph:
+    """``A[idx][:, idx]`` of one square CsrGraph (see ``induced_subgraphs``)."""
+    return induced_subgraphs([g], idx)[0]
+
+
+class collect_f:
+    """The reference's ``collect_f`` (HAN/utils/data_utils.py:92-101), the ``collate_fn`` of its
+    mini-batch loaders: same three constructor arguments, ``HGs_adj``, ``features`` (fp32) and
+    ``labels`` (int64), and ``__call__(data)`` returns ``([A[idx][:, idx] for A in HGs_adj],
+    features[idx], labels[idx])``. ``HGs`` is a ``HeteroGraph`` (iterated once, as the reference
+    does) or a list of ``CsrGraph``s, and then each slice is a ``CsrGraph`` [b, b] built by
+    ``induced_subgraphs``; a list of dense arrays keeps the reference's own line. ``device``:
+    where the graphs, features and labels live (default: where the graphs are)."""
+
+    def __init__(self, HGs, features, labels, device=None):
+        graphs = list(HGs)
+        if all(isinstance(g, CsrGraph) for g in graphs):
+            if device is None and graphs:
+                device = graphs[0].device
+            self.HGs_adj = [g if device is None or g.device == torch.device(device)
+                            else g.to(device) for g in graphs]
+            self._csr = True
+        else:
+            self.HGs_adj = [torch.as_tensor(g).to(device) if device is not None
+                            else torch.as_tensor(g) for g in graphs]
+            self._csr = False
+        self.features = torch.as_tensor(features).to(torch.float32)
+        self.labels = torch.as_tensor(labels).to(torch.int64)
+        if device is not None:
+            self.features, self.labels = self.features.to(device), self.labels.to(device)
+
+    def __call__(self, data):
+        idx = _batch_index(data, self.features.device)
+        if self._csr:
+            adj = induced_subgraphs(self.HGs_adj, idx)
+        else:
+            adj = [a[idx.to(a.device)][:, idx.to(a.device)] for a in self.HGs_adj]
+        return adj, self.features[idx], self.labels[idx]

@@ -1263,6 +1263,57 @@ int gnn_relation_product_fill(const int64_t* a_rowptr, const int32_t* a_col, int
                               int32_t* c_col, int64_t nnz_c, void* workspace,
                               int64_t workspace_bytes, void* stream);
 
+/*
+ * Induced subgraph on the device: C = A[idx][:, idx] as CSR -- the mini-batch slice of the
+ * reference's HAN loader (HAN/utils/data_utils.py:98-101, collect_f.__call__:
+ * HG_adj[idx][:, idx] on a dense N x N tensor), written as CSR from CSR.
+ *   A [n, n]: CSR, rowptr int64 [n + 1], col int32 [nnz] in any order within a row, val fp32
+ *     [nnz] or NULL. idx: int64 [b] on the device, ids in [0, n) in any order, an id may repeat.
+ *   C [b, b]: C[r, p] = A[idx[r], idx[p]]. Every stored entry of row idx[r] whose column id is
+ *     selected is carried once for every position p with idx[p] = that id, its value copied;
+ *     within a row of C the entries are in ASCENDING position order. For an A without a
+ *     repeated column inside a row this is the CSR of the dense slice read row-major, bit for
+ *     bit, and the same from run to run (integer atomics only, the result is a sorted sequence).
+ *   status: a device int32 the caller zeroed; bits are ORed in. With a bit set the outputs are
+ *     unspecified, but nothing is read or written out of bounds.
+ *       bit 0  an idx entry outside [0, n) (its row and its position are left out)
+ *       bit 1  a malformed rowptr span, or a column id outside [0, n), in a selected row
+ *       bit 2  the same (row, position) pair produced twice: a selected row of A repeats a
+ *              selected column. A refusal, not a summation (raised by the fill call).
+ * Three calls per batch, the library never allocates and NONE of them synchronises `stream`:
+ *   gnn_induced_subgraph_map: builds the id -> positions map of this batch in the workspace's
+ *     map part (a head per node, a next and a chain length per position: repeated ids chain).
+ *     Accepts a workspace with any previous content; call it again for the next batch.
+ *   gnn_induced_subgraph_count: writes c_rowptr [b + 1] (device); c_rowptr[b] is nnz(C).
+ *   gnn_induced_subgraph_fill: writes c_col [nnz_c] and, unless val or c_val is NULL, c_val
+ *     [nnz_c], recomputing each row from A, c_rowptr and the map: exactly
+ *     c_rowptr[r+1] - c_rowptr[r] entries for row r.
+ *   The map part is read-only after _map; the scratch part may be overwritten by any count or
+ *   fill. So M counts followed by M fills over M graphs [n, n] share one map and one workspace.
+ * Fill classes a row by its KEPT count c = c_rowptr[r+1] - c_rowptr[r], not by A's degree:
+ *   gnn_induced_subgraph_class_limits: *short_max = the largest c sorted by one wavefront in
+ *     registers (key = position << 32 | ordinal in A's row), *mid_max = the largest c sorted
+ *     by a workgroup in LDS; rows above it are ranked in a bitmap of b bits, which lives in
+ *     LDS while b <= *lds_bits and in per-workgroup bitmaps of the workspace above.
+ * Workspace: gnn_induced_subgraph_workspace_bytes(n, b) bytes, a function of (n, b) alone:
+ *   4 n + 8 b bytes of map, O(b) of scratch and, above lds_bits, a fixed number of b-bit bitmaps.
+ * Limits: n, b < 2^31 - 1 (else GNN_E_UNSUPPORTED, from the workspace query too; a negative
+ *   size -> GNN_E_ARG); a row of A holds fewer than 2^32 entries; nnz(C) may exceed 2^31
+ *   (64-bit offsets throughout). Null operands and a short workspace -> GNN_E_ARG.
+ */
+int64_t gnn_induced_subgraph_workspace_bytes(int64_t n, int64_t b);
+int gnn_induced_subgraph_class_limits(int64_t* short_max, int64_t* mid_max, int64_t* lds_bits);
+int gnn_induced_subgraph_map(const int64_t* idx, int64_t b, int64_t n, int32_t* status,
+                             void* workspace, int64_t workspace_bytes, void* stream);
+int gnn_induced_subgraph_count(const int64_t* rowptr, const int32_t* col, int64_t nnz, int64_t n,
+                               const int64_t* idx, int64_t b, int64_t* c_rowptr, int32_t* status,
+                               void* workspace, int64_t workspace_bytes, void* stream);
+int gnn_induced_subgraph_fill(const int64_t* rowptr, const int32_t* col, const float* val,
+                              int64_t nnz, int64_t n, const int64_t* idx, int64_t b,
+                              const int64_t* c_rowptr, int32_t* c_col, float* c_val,
+                              int64_t nnz_c, int32_t* status, void* workspace,
+                              int64_t workspace_bytes, void* stream);
+
 /* ---- CPython-exact host sampler (pysample.cpp; host memory, no stream) ----
  * Bit-exact restatement of the reference's host-side GraphSAGE sampling, which draws
  * from CPython's global `random` and iterates Python sets:
