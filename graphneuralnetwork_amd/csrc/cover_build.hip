@@ -19,15 +19,13 @@
 #include <rocprim/rocprim.hpp>
 
 #include "common.hpp"
+#include "host.hpp"
 
 namespace gnn {
 namespace cb {
 
 constexpr int kT = 256;
 constexpr int kMaxWorld = 64;
-
-static inline unsigned grid(int64_t n) { return static_cast<unsigned>((n + kT - 1) / kT); }
-static inline int64_t up(int64_t v) { return (v + 255) / 256 * 256; }
 
 struct Bounds {  // row boundaries by value (no host-to-device copy of a caller's array)
   int64_t b[kMaxWorld + 1];
@@ -39,16 +37,6 @@ struct Bounds {  // row boundaries by value (no host-to-device copy of a caller'
       if (b[mid] <= c) lo = mid; else hi = mid;
     }
     return lo;
-  }
-};
-
-struct Carve {
-  char* p;
-  int64_t used = 0;
-  template <class T> T* take(int64_t n) {
-    T* r = reinterpret_cast<T*>(p ? p + used : nullptr);
-    used += up((n > 0 ? n : 1) * static_cast<int64_t>(sizeof(T)));
-    return r;
   }
 };
 
@@ -136,21 +124,23 @@ static CoverWs cover_carve(void* ws, int64_t E, int64_t n, int64_t n_own, int wo
   Carve c{static_cast<char*>(ws)};
   CoverWs w{};
   const int64_t P = n_own * world;
-  w.e_row = c.take<int32_t>(E);
-  w.e_cls = c.take<uint8_t>(E);
-  w.cnt_pair = c.take<int32_t>(P);
-  w.hp = c.take<uint8_t>(P);
-  w.pk = c.take<uint8_t>(P);
+  // a rank without edges or rows still gets one element of each E- and P-sized piece
+  const int64_t e1 = E > 0 ? E : 1, p1 = P > 0 ? P : 1;
+  w.e_row = c.take<int32_t>(e1);
+  w.e_cls = c.take<uint8_t>(e1);
+  w.cnt_pair = c.take<int32_t>(p1);
+  w.hp = c.take<uint8_t>(p1);
+  w.pk = c.take<uint8_t>(p1);
   w.cnt_col = c.take<int32_t>(n);
   w.hx = c.take<uint8_t>(n);
   w.kpre = c.take<int64_t>(E + 1);
   w.xpre = c.take<int64_t>(E + 1);
   w.xrank = c.take<int64_t>(n + 1);
   w.pscan = c.take<int64_t>(P + 1);
-  w.p_idx0 = c.take<int64_t>(E);
-  w.p_idx1 = c.take<int64_t>(E);
-  w.p_key0 = c.take<uint64_t>(E);
-  w.p_key1 = c.take<uint64_t>(E);
+  w.p_idx0 = c.take<int64_t>(e1);
+  w.p_idx1 = c.take<int64_t>(e1);
+  w.p_key0 = c.take<uint64_t>(e1);
+  w.p_key1 = c.take<uint64_t>(e1);
   w.hp_cnt = c.take<int64_t>(n_own + 1);
   w.qb = c.take<int64_t>(2 * kMaxWorld);
   w.cnt = c.take<int64_t>(4);
@@ -382,18 +372,6 @@ __global__ void send_p_fill_kernel(const int64_t* __restrict__ slot_incl, const 
   sp_val[t] = pe_v[t];
 }
 
-#define CB_TRY(x)                                       \
-  do {                                                  \
-    hipError_t e_ = (x);                                \
-    if (e_ != hipSuccess) return static_cast<int>(e_);  \
-  } while (0)
-
-static int sync_read(const int64_t* dev, int64_t* host, int64_t count, hipStream_t s) {
-  hipError_t e = hipMemcpyAsync(host, dev, count * sizeof(int64_t), hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  return e == hipSuccess ? GNN_OK : static_cast<int>(e);
-}
-
 static bool read_bounds(const int64_t* bounds, int32_t world, int64_t n_rows, Bounds* B) {
   if (!bounds || world < 1 || world > kMaxWorld) return false;
   B->world = world;
@@ -427,85 +405,83 @@ extern "C" int gnn_cover_build(const int64_t* rowptr, const int32_t* col, int64_
   const int64_t r0 = B.b[rank], n_own = B.b[rank + 1] - r0;
   hipStream_t s = static_cast<hipStream_t>(stream);
   int64_t e01[2];
-  CB_TRY(hipMemcpyAsync(&e01[0], rowptr + r0, 8, hipMemcpyDeviceToHost, s));
-  CB_TRY(hipMemcpyAsync(&e01[1], rowptr + r0 + n_own, 8, hipMemcpyDeviceToHost, s));
-  CB_TRY(hipStreamSynchronize(s));
+  GNN_TRY(hipMemcpyAsync(&e01[0], rowptr + r0, 8, hipMemcpyDeviceToHost, s));
+  GNN_TRY(hipMemcpyAsync(&e01[1], rowptr + r0 + n_own, 8, hipMemcpyDeviceToHost, s));
+  GNN_TRY(hipStreamSynchronize(s));
   const int64_t e0 = e01[0], E = e01[1] - e01[0];
   if (E > 0 && !col) return GNN_E_ARG;
-  if (workspace_bytes < gnn_cover_workspace_bytes(n_rows, E, n_own, world)) return GNN_E_ARG;
-  for (int i = 0; i < 4 + 3 * world; ++i) counts[i] = 0;
+  if (E < 0) return GNN_E_ARG;  // gnn_cover_workspace_bytes' own refusal of a negative nnz_local
   CoverWs w = cover_carve(workspace, E, n_rows, n_own, world);
+  if (workspace_bytes < w.bytes) return GNN_E_ARG;
+  for (int i = 0; i < 4 + 3 * world; ++i) counts[i] = 0;
   const int64_t P = n_own * world;
-  CB_TRY(hipMemsetAsync(w.cnt_pair, 0, static_cast<size_t>(P) * 4, s));
-  CB_TRY(hipMemsetAsync(w.hp, 0, static_cast<size_t>(P), s));
-  CB_TRY(hipMemsetAsync(w.pk, 0, static_cast<size_t>(P), s));
-  CB_TRY(hipMemsetAsync(w.cnt_col, 0, static_cast<size_t>(n_rows) * 4, s));
-  CB_TRY(hipMemsetAsync(w.hx, 0, static_cast<size_t>(n_rows), s));
-  CB_TRY(hipMemsetAsync(w.qb, 0, 2 * kMaxWorld * 8, s));
-  CB_TRY(hipMemsetAsync(w.cnt, 0, 4 * 8, s));
-  CB_TRY(hipMemsetAsync(w.err, 0, 4, s));
+  GNN_TRY(hipMemsetAsync(w.cnt_pair, 0, static_cast<size_t>(P) * 4, s));
+  GNN_TRY(hipMemsetAsync(w.hp, 0, static_cast<size_t>(P), s));
+  GNN_TRY(hipMemsetAsync(w.pk, 0, static_cast<size_t>(P), s));
+  GNN_TRY(hipMemsetAsync(w.cnt_col, 0, static_cast<size_t>(n_rows) * 4, s));
+  GNN_TRY(hipMemsetAsync(w.hx, 0, static_cast<size_t>(n_rows), s));
+  GNN_TRY(hipMemsetAsync(w.qb, 0, 2 * kMaxWorld * 8, s));
+  GNN_TRY(hipMemsetAsync(w.cnt, 0, 4 * 8, s));
+  GNN_TRY(hipMemsetAsync(w.err, 0, 4, s));
   if (E > 0) {
-    hipLaunchKernelGGL(cover_count_kernel, dim3(grid(E)), dim3(kT), 0, s, rowptr, col, r0, n_own, e0,
+    hipLaunchKernelGGL(cover_count_kernel, dim3(blocks(E, kT)), dim3(kT), 0, s, rowptr, col, r0, n_own, e0,
                        E, B, w.e_row, w.e_cls, w.cnt_pair, w.cnt_col, w.err);
     int32_t herr = 0;
-    CB_TRY(hipMemcpyAsync(&herr, w.err, 4, hipMemcpyDeviceToHost, s));
-    CB_TRY(hipStreamSynchronize(s));
+    GNN_TRY(sync_read(w.err, &herr, 1, s));
     if (herr) return GNN_E_ARG;  // a column id outside [0, n_rows)
-    hipLaunchKernelGGL(cover_rule_kernel, dim3(grid(E)), dim3(kT), 0, s, col, e0, E, n_own, B, w.e_row,
+    hipLaunchKernelGGL(cover_rule_kernel, dim3(blocks(E, kT)), dim3(kT), 0, s, col, e0, E, n_own, B, w.e_row,
                        w.e_cls, w.cnt_pair, w.cnt_col, w.hp);
-    hipLaunchKernelGGL(cover_cols_kernel, dim3(grid(E)), dim3(kT), 0, s, col, e0, E, n_own, B, w.e_row,
+    hipLaunchKernelGGL(cover_cols_kernel, dim3(blocks(E, kT)), dim3(kT), 0, s, col, e0, E, n_own, B, w.e_row,
                        w.e_cls, w.hp, w.hx);
-    hipLaunchKernelGGL(cover_final_kernel, dim3(grid(E)), dim3(kT), 0, s, col, e0, E, n_own, B,
+    hipLaunchKernelGGL(cover_final_kernel, dim3(blocks(E, kT)), dim3(kT), 0, s, col, e0, E, n_own, B,
                        w.e_row, w.e_cls, w.hp, w.hx, w.pk);
   }
   // edge prefixes of the interior and the feature-covered classes (their CSR offsets)
   size_t tb = w.temp_bytes;
   const auto k_it = rocprim::make_transform_iterator(Count(0), ClsIs{w.e_cls, kInterior, E});
-  CB_TRY(rocprim::exclusive_scan(w.temp, tb, k_it, w.kpre, int64_t(0), static_cast<size_t>(E + 1),
+  GNN_TRY(rocprim::exclusive_scan(w.temp, tb, k_it, w.kpre, int64_t(0), static_cast<size_t>(E + 1),
                                  rocprim::plus<int64_t>(), s));
   tb = w.temp_bytes;
   const auto x_it = rocprim::make_transform_iterator(Count(0), ClsIs{w.e_cls, kFeature, E});
-  CB_TRY(rocprim::exclusive_scan(w.temp, tb, x_it, w.xpre, int64_t(0), static_cast<size_t>(E + 1),
+  GNN_TRY(rocprim::exclusive_scan(w.temp, tb, x_it, w.xpre, int64_t(0), static_cast<size_t>(E + 1),
                                  rocprim::plus<int64_t>(), s));
   // requested columns (ascending global ids = grouped by owner) and their ranks
   tb = w.temp_bytes;
   const auto h_it = rocprim::make_transform_iterator(Count(0), ByteAt{w.hx, n_rows});
-  CB_TRY(rocprim::exclusive_scan(w.temp, tb, h_it, w.xrank, int64_t(0), static_cast<size_t>(n_rows + 1),
+  GNN_TRY(rocprim::exclusive_scan(w.temp, tb, h_it, w.xrank, int64_t(0), static_cast<size_t>(n_rows + 1),
                                  rocprim::plus<int64_t>(), s));
   // partial rows: one per (owner, row) pair with a partial edge, in (owner, row) order
   tb = w.temp_bytes;
   const auto p_it = rocprim::make_transform_iterator(Count(0), ByteAt{w.pk, P});
-  CB_TRY(rocprim::exclusive_scan(w.temp, tb, p_it, w.pscan, int64_t(0), static_cast<size_t>(P + 1),
+  GNN_TRY(rocprim::exclusive_scan(w.temp, tb, p_it, w.pscan, int64_t(0), static_cast<size_t>(P + 1),
                                  rocprim::plus<int64_t>(), s));
   // partial edges: edge order, then a stable sort by (owner, row)
   int64_t np = 0;
   if (E > 0) {
     tb = w.temp_bytes;
     const auto f_it = rocprim::make_transform_iterator(Count(0), ClsFlag{w.e_cls, kPartial});
-    CB_TRY(rocprim::select(w.temp, tb, Count(0), f_it, w.p_idx0, w.cnt, static_cast<size_t>(E), s));
-    int rc = sync_read(w.cnt, &np, 1, s);
-    if (rc != GNN_OK) return rc;
+    GNN_TRY(rocprim::select(w.temp, tb, Count(0), f_it, w.p_idx0, w.cnt, static_cast<size_t>(E), s));
+    GNN_TRY(sync_read(w.cnt, &np, 1, s));
   }
   if (np > 0) {
-    hipLaunchKernelGGL(cover_pkeys_kernel, dim3(grid(np)), dim3(kT), 0, s, w.p_idx0, w.cnt, col, e0,
+    hipLaunchKernelGGL(cover_pkeys_kernel, dim3(blocks(np, kT)), dim3(kT), 0, s, w.p_idx0, w.cnt, col, e0,
                        n_own, B, w.e_row, w.p_key0);
     unsigned bits = 1;
     while (bits < 64 && (static_cast<uint64_t>(1) << bits) < static_cast<uint64_t>(P)) ++bits;
     tb = w.temp_bytes;
-    CB_TRY(rocprim::radix_sort_pairs(w.temp, tb, w.p_key0, w.p_key1, w.p_idx0, w.p_idx1,
+    GNN_TRY(rocprim::radix_sort_pairs(w.temp, tb, w.p_key0, w.p_key1, w.p_idx0, w.p_idx1,
                                      static_cast<size_t>(np), 0, bits, s));
-    hipLaunchKernelGGL(cover_qbounds_kernel, dim3(grid(np)), dim3(kT), 0, s, w.p_key1, np, n_own, w.qb);
+    hipLaunchKernelGGL(cover_qbounds_kernel, dim3(blocks(np, kT)), dim3(kT), 0, s, w.p_key1, np, n_own, w.qb);
   }
   if (n_own > 0)
-    hipLaunchKernelGGL(cover_hp_count_kernel, dim3(grid(n_own)), dim3(kT), 0, s, w.pk, n_own, world,
+    hipLaunchKernelGGL(cover_hp_count_kernel, dim3(blocks(n_own, kT)), dim3(kT), 0, s, w.pk, n_own, world,
                        w.hp_cnt);
   // counts: [0] interior nnz, [1] requested columns, [2] halo_x nnz, [3] partial rows,
   // [4 + q] feature rows asked of q, [4 + W + q] partial rows asked of q, [4 + 2W + q] their edges
   // -- gathered on the device and read back once (4 W + 6 separate reads before)
   hipLaunchKernelGGL(cover_counts_kernel, dim3(1), dim3(kMaxWorld), 0, s, w.kpre, w.xpre, w.xrank,
                      w.pscan, w.qb, E, n_rows, P, n_own, B, w.out);
-  int rc = sync_read(w.out, counts, 4 + 3 * static_cast<int64_t>(world), s);
-  if (rc != GNN_OK) return rc;
+  GNN_TRY(sync_read(w.out, counts, 4 + 3 * static_cast<int64_t>(world), s));
   return launch_status();
 }
 
@@ -523,9 +499,9 @@ extern "C" int gnn_cover_fill(const void* workspace, const int64_t* rowptr, cons
   const int64_t r0 = B.b[rank], n_own = B.b[rank + 1] - r0;
   hipStream_t s = static_cast<hipStream_t>(stream);
   int64_t e01[2];
-  CB_TRY(hipMemcpyAsync(&e01[0], rowptr + r0, 8, hipMemcpyDeviceToHost, s));
-  CB_TRY(hipMemcpyAsync(&e01[1], rowptr + r0 + n_own, 8, hipMemcpyDeviceToHost, s));
-  CB_TRY(hipStreamSynchronize(s));
+  GNN_TRY(hipMemcpyAsync(&e01[0], rowptr + r0, 8, hipMemcpyDeviceToHost, s));
+  GNN_TRY(hipMemcpyAsync(&e01[1], rowptr + r0 + n_own, 8, hipMemcpyDeviceToHost, s));
+  GNN_TRY(hipStreamSynchronize(s));
   const int64_t e0 = e01[0], E = e01[1] - e01[0];
   CoverWs w = cover_carve(const_cast<void*>(workspace), E, n_rows, n_own, world);
   int64_t np = 0;
@@ -534,36 +510,57 @@ extern "C" int gnn_cover_fill(const void* workspace, const int64_t* rowptr, cons
       (counts[2] && (!hx_col || !hx_val)) || (np && (!pe_i || !pe_j || !pe_v)) ||
       (counts[3] && (!hp_col || !hp_val)))
     return GNN_E_ARG;
-  hipLaunchKernelGGL(cover_fill_rowptr_kernel, dim3(grid(n_own + 1)), dim3(kT), 0, s, rowptr, r0, n_own,
+  hipLaunchKernelGGL(cover_fill_rowptr_kernel, dim3(blocks(n_own + 1, kT)), dim3(kT), 0, s, rowptr, r0, n_own,
                      e0, w.kpre, w.xpre, int_rowptr, hx_rowptr);
   if (E > 0)
-    hipLaunchKernelGGL(cover_fill_edges_kernel, dim3(grid(E)), dim3(kT), 0, s, col, val, e0, E, r0,
+    hipLaunchKernelGGL(cover_fill_edges_kernel, dim3(blocks(E, kT)), dim3(kT), 0, s, col, val, e0, E, r0,
                        w.e_row, w.e_cls, w.kpre, w.xpre, w.xrank, int_col, int_val, hx_col, hx_val);
   if (counts[1] > 0) {
     size_t tb = w.temp_bytes;
     const auto h_it = rocprim::make_transform_iterator(Count(0), ByteAt{w.hx, n_rows});
-    CB_TRY(rocprim::select(w.temp, tb, Count(0), h_it, xcols, w.cnt + 1, static_cast<size_t>(n_rows), s));
+    GNN_TRY(rocprim::select(w.temp, tb, Count(0), h_it, xcols, w.cnt + 1, static_cast<size_t>(n_rows), s));
   }
   if (np > 0)
-    hipLaunchKernelGGL(cover_fill_pedges_kernel, dim3(grid(np)), dim3(kT), 0, s, w.p_idx1, np, col, val,
+    hipLaunchKernelGGL(cover_fill_pedges_kernel, dim3(blocks(np, kT)), dim3(kT), 0, s, w.p_idx1, np, col, val,
                        e0, r0, w.e_row, pe_i, pe_j, pe_v);
   size_t tb = w.temp_bytes;
   const auto a_it = rocprim::make_transform_iterator(Count(0), Arr{w.hp_cnt, n_own});
-  CB_TRY(rocprim::exclusive_scan(w.temp, tb, a_it, hp_rowptr, int64_t(0), static_cast<size_t>(n_own + 1),
+  GNN_TRY(rocprim::exclusive_scan(w.temp, tb, a_it, hp_rowptr, int64_t(0), static_cast<size_t>(n_own + 1),
                                  rocprim::plus<int64_t>(), s));
   if (n_own > 0 && counts[3] > 0)
-    hipLaunchKernelGGL(cover_fill_halo_p_kernel, dim3(grid(n_own)), dim3(kT), 0, s, w.pk, w.pscan, n_own,
+    hipLaunchKernelGGL(cover_fill_halo_p_kernel, dim3(blocks(n_own, kT)), dim3(kT), 0, s, w.pk, w.pscan, n_own,
                        world, hp_rowptr, hp_col, hp_val);
   return launch_status();
 }
 
-extern "C" int64_t gnn_cover_send_workspace_bytes(int64_t n_edges) {
-  if (n_edges < 0) return GNN_E_ARG;
+// the workspace of gnn_cover_send_partials over m received edges
+struct CoverSendWs {
+  int64_t* slot;  // [m] inclusive count of (peer, row) slot heads
+  int32_t* err;   // [1] a column outside this rank's rows
+  void* temp;
+  size_t temp_bytes;
+  int64_t bytes;
+};
+
+static CoverSendWs cover_send_carve(void* ws, int64_t m) {
+  Carve c{static_cast<char*>(ws)};
+  CoverSendWs w{};
+  const int64_t m1 = m > 0 ? m : 1;
+  w.slot = c.take<int64_t>(m1);
+  w.err = c.take<int32_t>(1);
   size_t t = 0;
   const auto h_it = rocprim::make_transform_iterator(Count(0), SlotHead{nullptr, Offsets{}});
   (void)rocprim::inclusive_scan(nullptr, t, h_it, static_cast<int64_t*>(nullptr),
-                                static_cast<size_t>(n_edges > 0 ? n_edges : 1), rocprim::plus<int64_t>());
-  return up((n_edges > 0 ? n_edges : 1) * 8) + 256 + up(static_cast<int64_t>(t) + 256);
+                                static_cast<size_t>(m1), rocprim::plus<int64_t>());
+  w.temp_bytes = t + 256;
+  w.temp = c.take<char>(static_cast<int64_t>(w.temp_bytes));
+  w.bytes = c.used;
+  return w;
+}
+
+extern "C" int64_t gnn_cover_send_workspace_bytes(int64_t n_edges) {
+  if (n_edges < 0) return GNN_E_ARG;
+  return cover_send_carve(nullptr, n_edges).bytes;
 }
 
 extern "C" int gnn_cover_send_partials(const int64_t* pe_i, const int64_t* pe_j, const float* pe_v,
@@ -582,31 +579,27 @@ extern "C" int gnn_cover_send_partials(const int64_t* pe_i, const int64_t* pe_j,
     O.o[q + 1] = O.o[q] + recv_edges[q];
   }
   const int64_t m = O.o[world];
-  if (workspace_bytes < gnn_cover_send_workspace_bytes(m)) return GNN_E_ARG;
+  CoverSendWs w = cover_send_carve(workspace, m);
+  if (workspace_bytes < w.bytes) return GNN_E_ARG;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (m == 0) {
     if (n_p_send != 0) return GNN_E_ARG;
-    CB_TRY(hipMemsetAsync(sp_rowptr, 0, 8, s));
+    GNN_TRY(hipMemsetAsync(sp_rowptr, 0, 8, s));
     return launch_status();
   }
   if (!pe_i || !pe_j || !pe_v || !sp_col || !sp_val) return GNN_E_ARG;
-  char* p = static_cast<char*>(workspace);
-  int64_t* slot = reinterpret_cast<int64_t*>(p);
-  int32_t* err = reinterpret_cast<int32_t*>(p + up(m * 8));
-  void* temp = p + up(m * 8) + 256;
-  size_t tb = static_cast<size_t>(workspace_bytes - up(m * 8) - 256);
-  CB_TRY(hipMemsetAsync(err, 0, 4, s));
+  size_t tb = w.temp_bytes;
+  GNN_TRY(hipMemsetAsync(w.err, 0, 4, s));
   const auto h_it = rocprim::make_transform_iterator(Count(0), SlotHead{pe_i, O});
-  CB_TRY(rocprim::inclusive_scan(temp, tb, h_it, slot, static_cast<size_t>(m), rocprim::plus<int64_t>(), s));
+  GNN_TRY(rocprim::inclusive_scan(w.temp, tb, h_it, w.slot, static_cast<size_t>(m),
+                                  rocprim::plus<int64_t>(), s));
   int64_t n_slots = 0;
-  int rc = sync_read(slot + m - 1, &n_slots, 1, s);
-  if (rc != GNN_OK) return rc;
+  GNN_TRY(sync_read(w.slot + m - 1, &n_slots, 1, s));
   if (n_slots != n_p_send) return GNN_E_ARG;  // the handshake's partial-row count disagrees
-  hipLaunchKernelGGL(send_p_fill_kernel, dim3(grid(m)), dim3(kT), 0, s, slot, pe_i, pe_j, pe_v, m, O, r0,
-                     n_own, sp_rowptr, sp_col, sp_val, err);
+  hipLaunchKernelGGL(send_p_fill_kernel, dim3(blocks(m, kT)), dim3(kT), 0, s, w.slot, pe_i, pe_j, pe_v,
+                     m, O, r0, n_own, sp_rowptr, sp_col, sp_val, w.err);
   int32_t herr = 0;
-  CB_TRY(hipMemcpyAsync(&herr, err, 4, hipMemcpyDeviceToHost, s));
-  CB_TRY(hipStreamSynchronize(s));
+  GNN_TRY(sync_read(w.err, &herr, 1, s));
   if (herr) return GNN_E_ARG;  // a column outside this rank's rows
   return launch_status();
 }

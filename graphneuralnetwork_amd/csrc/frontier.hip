@@ -13,6 +13,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "common.hpp"
+#include "host.hpp"
 #include "sample_kernels.hpp"
 
 namespace gnn {
@@ -29,8 +30,6 @@ namespace gnn {
 constexpr int kHotWords = 2048;                 // 8 KiB of LDS per workgroup
 constexpr int64_t kHotIds = 32 * kHotWords;     // ids 0 .. 65535
 constexpr int kMarkBlocks = 256;                // workgroups of a mark launch (grid-stride)
-
-static inline int64_t fr_align_bytes(int64_t v) { return (v + 255) / 256 * 256; }
 
 __device__ __forceinline__ void mark_bit(uint32_t* bits, int64_t v) {
   uint32_t* w = bits + (v >> 5);
@@ -218,31 +217,22 @@ struct SampleWs {
   uint32_t* pre;    // [n_words] frontier position of each marked word's first id
   uint64_t* tile;   // [n_tiles] look-back words {tag:30 | kind:2 | value:32}
   uint64_t* ctl;    // [0] tag base (bumped by L per call), [1] tile ticket of the next scan
+  int64_t bytes;
 };
 
 static int64_t sw_tiles(int64_t n_words) { return (n_words + kScanTileWords - 1) / kScanTileWords; }
 
-static int64_t sw_bytes(int64_t n_graph, SampleWs* w, char* base) {
+static SampleWs sw_carve(void* ws, int64_t n_graph) {
+  Carve c{static_cast<char*>(ws)};
+  SampleWs w{};
   const int64_t n_words = (n_graph + 31) / 32;
-  int64_t off = 0;
-  auto take = [&](int64_t bytes) {
-    char* p = base ? base + off : nullptr;
-    off += fr_align_bytes(bytes);
-    return p;
-  };
-  char* f = take(32 * n_words);
-  char* b = take(4 * n_words);
-  char* pr = take(4 * n_words);
-  char* t = take(8 * sw_tiles(n_words));
-  char* c = take(64);
-  if (w) {
-    w->flags = reinterpret_cast<uint8_t*>(f);
-    w->bits = reinterpret_cast<uint32_t*>(b);
-    w->pre = reinterpret_cast<uint32_t*>(pr);
-    w->tile = reinterpret_cast<uint64_t*>(t);
-    w->ctl = reinterpret_cast<uint64_t*>(c);
-  }
-  return off;
+  w.flags = c.take<uint8_t>(32 * n_words);
+  w.bits = c.take<uint32_t>(n_words);
+  w.pre = c.take<uint32_t>(n_words);
+  w.tile = c.take<uint64_t>(sw_tiles(n_words));
+  w.ctl = c.take<uint64_t>(8);
+  w.bytes = c.used;
+  return w;
 }
 
 struct HopArgs {
@@ -465,13 +455,6 @@ __global__ __launch_bounds__(kScanThreads) void batch_scan_kernel(uint8_t* __res
   }
 }
 
-static unsigned fr_grid(int64_t n) {
-  const int64_t b = (n + 255) / 256;
-  return static_cast<unsigned>(b < 1 ? 1 : (b > 65536 ? 65536 : b));
-}
-
-static int64_t fr_align(int64_t v) { return (v + 255) / 256 * 256; }
-
 struct PopcOp {
   __host__ __device__ uint32_t operator()(uint32_t w) const {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -501,18 +484,23 @@ struct FrontierWs {
   uint32_t* pre;
   void* temp;
   size_t temp_bytes;
+  int64_t bytes;
 };
 
-static FrontierWs fr_layout(void* ws, int64_t n_nodes, int64_t ws_bytes) {
+// emit and rank read only bits and pre, kept from the build: sized == false skips rocPRIM's
+// size queries and leaves temp_bytes and bytes at 0
+static FrontierWs fr_carve(void* ws, int64_t n_nodes, bool sized = true) {
+  Carve c{static_cast<char*>(ws)};
+  FrontierWs f{};
   const int64_t n_words = (n_nodes + 31) / 32;
-  const int64_t seg = fr_align(4 * n_words);
-  char* p = static_cast<char*>(ws);
-  FrontierWs f;
-  f.bits = reinterpret_cast<uint32_t*>(p);
-  f.cnt = reinterpret_cast<uint32_t*>(p + seg);
-  f.pre = reinterpret_cast<uint32_t*>(p + 2 * seg);
-  f.temp = p + 3 * seg;
-  f.temp_bytes = ws_bytes > 3 * seg ? static_cast<size_t>(ws_bytes - 3 * seg) : 0;
+  f.bits = c.take<uint32_t>(n_words);
+  f.cnt = c.take<uint32_t>(n_words);
+  f.pre = c.take<uint32_t>(n_words);
+  if (!sized) return f;
+  f.temp_bytes = fr_scan_temp(n_words);
+  f.temp = c.raw(static_cast<int64_t>(f.temp_bytes));
+  c.raw(256);
+  f.bytes = c.used;
   return f;
 }
 
@@ -522,8 +510,7 @@ using namespace gnn;
 
 extern "C" int64_t gnn_frontier_workspace_bytes(int64_t n_nodes) {
   if (n_nodes < 1) return GNN_E_ARG;
-  const int64_t n_words = (n_nodes + 31) / 32;
-  return 3 * fr_align(4 * n_words) + static_cast<int64_t>(fr_scan_temp(n_words)) + 256;
+  return fr_carve(nullptr, n_nodes).bytes;
 }
 
 extern "C" int gnn_frontier_build(const int64_t* ids_a, int64_t n_a, const int64_t* ids_b,
@@ -534,20 +521,18 @@ extern "C" int gnn_frontier_build(const int64_t* ids_a, int64_t n_a, const int64
       (n_a > 0 && !ids_a) || (n_b > 0 && !ids_b))
     return GNN_E_ARG;
   if (n_a + n_b > 0xffffffffLL) return GNN_E_UNSUPPORTED;  // 32-bit word prefixes
-  if (workspace_bytes < gnn_frontier_workspace_bytes(n_nodes)) return GNN_E_ARG;
+  FrontierWs f = fr_carve(workspace, n_nodes);
+  if (workspace_bytes < f.bytes) return GNN_E_ARG;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int64_t n_words = (n_nodes + 31) / 32;
-  FrontierWs f = fr_layout(workspace, n_nodes, workspace_bytes);
-  hipError_t e = hipMemsetAsync(f.bits, 0, 4 * n_words, s);
-  if (e != hipSuccess) return static_cast<int>(e);
+  GNN_TRY(hipMemsetAsync(f.bits, 0, 4 * n_words, s));
   if (n_a + n_b > 0)
     hipLaunchKernelGGL(frontier_mark_kernel, dim3(mark_grid(n_a + n_b)), dim3(256), 0, s, ids_a,
                        n_a, ids_b, n_b, n_nodes, f.bits, err_flag);
-  hipLaunchKernelGGL(frontier_popc_kernel, dim3(fr_grid(n_words)), dim3(256), 0, s, f.bits,
+  hipLaunchKernelGGL(frontier_popc_kernel, dim3(blocks_capped(n_words)), dim3(256), 0, s, f.bits,
                      n_words, f.cnt);
-  e = rocprim::exclusive_scan(f.temp, f.temp_bytes, f.cnt, f.pre, 0u,
-                              static_cast<size_t>(n_words), rocprim::plus<uint32_t>(), s);
-  if (e != hipSuccess) return static_cast<int>(e);
+  GNN_TRY(rocprim::exclusive_scan(f.temp, f.temp_bytes, f.cnt, f.pre, 0u,
+                                  static_cast<size_t>(n_words), rocprim::plus<uint32_t>(), s));
   hipLaunchKernelGGL(frontier_count_kernel, dim3(1), dim3(64), 0, s, f.cnt, f.pre, n_words, count);
   return launch_status();
 }
@@ -556,8 +541,8 @@ extern "C" int gnn_frontier_emit(int64_t n_nodes, const void* workspace, int64_t
                                  void* stream) {
   if (n_nodes < 1 || !workspace || !frontier) return GNN_E_ARG;
   const int64_t n_words = (n_nodes + 31) / 32;
-  FrontierWs f = fr_layout(const_cast<void*>(workspace), n_nodes, 0);
-  hipLaunchKernelGGL(frontier_emit_kernel, dim3(fr_grid(n_words)), dim3(256), 0,
+  FrontierWs f = fr_carve(const_cast<void*>(workspace), n_nodes, false);
+  hipLaunchKernelGGL(frontier_emit_kernel, dim3(blocks_capped(n_words)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), f.bits, f.pre, n_words, frontier);
   return launch_status();
 }
@@ -566,15 +551,15 @@ extern "C" int gnn_frontier_rank(const int64_t* ids, int64_t n, int64_t n_nodes,
                                  const void* workspace, int64_t* pos, void* stream) {
   if (n < 0 || n_nodes < 1 || !workspace || (n > 0 && (!ids || !pos))) return GNN_E_ARG;
   if (n == 0) return GNN_OK;
-  FrontierWs f = fr_layout(const_cast<void*>(workspace), n_nodes, 0);
-  hipLaunchKernelGGL(frontier_rank_kernel, dim3(fr_grid(n)), dim3(256), 0,
+  FrontierWs f = fr_carve(const_cast<void*>(workspace), n_nodes, false);
+  hipLaunchKernelGGL(frontier_rank_kernel, dim3(blocks_capped(n)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), ids, n, n_nodes, f.bits, f.pre, pos);
   return launch_status();
 }
 
 extern "C" int64_t gnn_sample_layers_workspace_bytes(int64_t n_graph) {
   if (n_graph < 1) return GNN_E_ARG;
-  return sw_bytes(n_graph, nullptr, nullptr);
+  return sw_carve(nullptr, n_graph).bytes;
 }
 
 template <int LPN>
@@ -605,7 +590,8 @@ extern "C" int gnn_sample_layers(const int64_t* rowptr, const int32_t* col, int6
       !fanouts || !layer_seeds || !caps || !nbrs || !stat || !workspace)
     return GNN_E_ARG;
   if (n_layers > 1 && (!layers || !center_maps || !neigh_maps)) return GNN_E_ARG;
-  if (workspace_bytes < gnn_sample_layers_workspace_bytes(n_graph)) return GNN_E_ARG;
+  SampleWs w = sw_carve(workspace, n_graph);
+  if (workspace_bytes < w.bytes) return GNN_E_ARG;
   if (caps[0] != n_seeds) return GNN_E_ARG;
   for (int i = 0; i < n_layers; ++i) {
     if (fanouts[i] < 1 || caps[i] < 1 || !nbrs[i]) return GNN_E_ARG;
@@ -620,8 +606,6 @@ extern "C" int gnn_sample_layers(const int64_t* rowptr, const int32_t* col, int6
   }
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int64_t n_words = (n_graph + 31) / 32;
-  SampleWs w;
-  sw_bytes(n_graph, &w, static_cast<char*>(workspace));
   int32_t* err = reinterpret_cast<int32_t*>(stat + n_layers);  // low word of the last entry
   if (n_layers == 1) {  // one hop: no frontier; the sizes / error word first
     hipLaunchKernelGGL(batch_init_kernel, dim3(1), dim3(128), 0, s, stat, n_layers, n_seeds);

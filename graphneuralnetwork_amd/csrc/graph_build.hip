@@ -19,6 +19,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "common.hpp"
+#include "host.hpp"
 
 namespace gnn {
 
@@ -32,14 +33,13 @@ struct BuildWs {
   void* temp;
   size_t temp_bytes;
   int64_t cap;
+  int64_t bytes;
 };
 
 struct RowOfKey {
   uint64_t n;
   __host__ __device__ uint64_t operator()(uint64_t k) const { return k / n; }
 };
-
-static int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
 
 static int64_t build_capacity(int64_t n_edges, int64_t n_nodes) { return 2 * n_edges + n_nodes; }
 
@@ -85,24 +85,19 @@ static size_t temp_bytes_for(int64_t cap, int64_t n) {
 }
 
 static BuildWs carve(void* ws, int64_t n_edges, int64_t n_nodes) {
+  Carve c{static_cast<char*>(ws)};
   BuildWs w{};
   w.cap = build_capacity(n_edges, n_nodes);
-  char* p = static_cast<char*>(ws);
-  const int64_t kb = align_up(w.cap * 8, 256);
-  w.k0 = reinterpret_cast<uint64_t*>(p);
-  p += kb;
-  w.k1 = reinterpret_cast<uint64_t*>(p);
-  p += kb;
-  w.v0 = reinterpret_cast<double*>(p);
-  p += kb;
-  w.v1 = reinterpret_cast<double*>(p);
-  p += kb;
-  w.count = reinterpret_cast<int64_t*>(p);
-  p += 256;
-  w.err = reinterpret_cast<int32_t*>(p);
-  p += 256;
-  w.temp = p;
+  w.k0 = c.take<uint64_t>(w.cap);
+  w.k1 = c.take<uint64_t>(w.cap);
+  w.v0 = c.take<double>(w.cap);
+  w.v1 = c.take<double>(w.cap);
+  w.count = c.take<int64_t>(4);
+  w.err = c.take<int32_t>(1);
   w.temp_bytes = temp_bytes_for(w.cap, n_nodes);
+  w.temp = c.raw(static_cast<int64_t>(w.temp_bytes));
+  c.raw(256);
+  w.bytes = c.used;
   return w;
 }
 
@@ -181,23 +176,13 @@ __global__ void emit_csr_kernel(const uint64_t* __restrict__ keys, const double*
   if (i == nnz - 1) rowptr[n] = nnz;
 }
 
-static inline unsigned grid_for(int64_t n) { return static_cast<unsigned>((n + 255) / 256); }
-
-static int read_count(const int64_t* dev, int64_t* host, hipStream_t s) {
-  hipError_t e = hipMemcpyAsync(host, dev, sizeof(int64_t), hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  return e == hipSuccess ? GNN_OK : static_cast<int>(e);
-}
-
 }  // namespace gnn
 
 using namespace gnn;
 
 extern "C" int64_t gnn_gcn_adjacency_workspace_bytes(int64_t n_edges, int64_t n_nodes) {
   if (n_edges < 0 || n_nodes < 1) return GNN_E_ARG;
-  const int64_t cap = build_capacity(n_edges, n_nodes);
-  return 4 * align_up(cap * 8, 256) + 512 +
-         static_cast<int64_t>(temp_bytes_for(cap, n_nodes)) + 256;
+  return carve(nullptr, n_edges, n_nodes).bytes;
 }
 
 extern "C" int gnn_gcn_adjacency_build(const int64_t* src, const int64_t* dst, int64_t n_edges,
@@ -207,76 +192,64 @@ extern "C" int gnn_gcn_adjacency_build(const int64_t* src, const int64_t* dst, i
     return GNN_E_ARG;
   if (n_nodes > 0x7fffffffLL || static_cast<__int128>(n_nodes) * n_nodes > (static_cast<__int128>(1) << 63))
     return GNN_E_UNSUPPORTED;
-  if (workspace_bytes < gnn_gcn_adjacency_workspace_bytes(n_edges, n_nodes)) return GNN_E_ARG;
-  hipStream_t s = static_cast<hipStream_t>(stream);
   BuildWs w = carve(workspace, n_edges, n_nodes);
+  if (workspace_bytes < w.bytes) return GNN_E_ARG;
+  hipStream_t s = static_cast<hipStream_t>(stream);
   const int64_t n = n_nodes;
   const unsigned bits = key_bits(n > 1 ? n : 2);
-  hipError_t e = hipMemsetAsync(w.err, 0, sizeof(int32_t), s);
-  if (e != hipSuccess) return static_cast<int>(e);
+  GNN_TRY(hipMemsetAsync(w.err, 0, sizeof(int32_t), s));
   int64_t u = 0;
-  int rc;
   size_t tb = w.temp_bytes;
   if (n_edges > 0) {
     // A: duplicate edges summed
-    hipLaunchKernelGGL(make_keys_kernel, dim3(grid_for(n_edges)), dim3(256), 0, s, src, dst,
+    hipLaunchKernelGGL(make_keys_kernel, dim3(blocks(n_edges, 256)), dim3(256), 0, s, src, dst,
                        n_edges, n, w.k0, w.v1, w.err);
-    e = rocprim::radix_sort_keys(w.temp, tb, w.k0, w.k1, static_cast<size_t>(n_edges), 0, bits, s);
-    if (e != hipSuccess) return static_cast<int>(e);
+    GNN_TRY(rocprim::radix_sort_keys(w.temp, tb, w.k0, w.k1, static_cast<size_t>(n_edges), 0, bits, s));
     tb = w.temp_bytes;
-    e = rocprim::deterministic_reduce_by_key(w.temp, tb, w.k1, w.v1, static_cast<size_t>(n_edges),
-                                             w.k0, w.v0, w.count, rocprim::plus<double>(),
-                                             rocprim::equal_to<uint64_t>(), s);
-    if (e != hipSuccess) return static_cast<int>(e);
-    if ((rc = read_count(w.count, &u, s)) != GNN_OK) return rc;
+    GNN_TRY(rocprim::deterministic_reduce_by_key(w.temp, tb, w.k1, w.v1, static_cast<size_t>(n_edges),
+                                                 w.k0, w.v0, w.count, rocprim::plus<double>(),
+                                                 rocprim::equal_to<uint64_t>(), s));
+    GNN_TRY(sync_read(w.count, &u, 1, s));
     int32_t herr = 0;
-    e = hipMemcpy(&herr, w.err, sizeof(int32_t), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return static_cast<int>(e);
+    GNN_TRY(hipMemcpy(&herr, w.err, sizeof(int32_t), hipMemcpyDeviceToHost));
     if (herr) return GNN_E_ARG;  // an endpoint outside [0, n)
     // A_sym = max(A, A^T)
-    hipLaunchKernelGGL(append_transpose_kernel, dim3(grid_for(u)), dim3(256), 0, s, w.k0, w.v0,
+    hipLaunchKernelGGL(append_transpose_kernel, dim3(blocks(u, 256)), dim3(256), 0, s, w.k0, w.v0,
                        w.count, n);
     tb = w.temp_bytes;
-    e = rocprim::radix_sort_pairs(w.temp, tb, w.k0, w.k1, w.v0, w.v1, static_cast<size_t>(2 * u), 0,
-                                  bits, s);
-    if (e != hipSuccess) return static_cast<int>(e);
+    GNN_TRY(rocprim::radix_sort_pairs(w.temp, tb, w.k0, w.k1, w.v0, w.v1, static_cast<size_t>(2 * u), 0,
+                                      bits, s));
     tb = w.temp_bytes;
-    e = rocprim::reduce_by_key(w.temp, tb, w.k1, w.v1, static_cast<size_t>(2 * u), w.k0, w.v0,
-                               w.count, rocprim::maximum<double>(), rocprim::equal_to<uint64_t>(), s);
-    if (e != hipSuccess) return static_cast<int>(e);
-    if ((rc = read_count(w.count, &u, s)) != GNN_OK) return rc;
+    GNN_TRY(rocprim::reduce_by_key(w.temp, tb, w.k1, w.v1, static_cast<size_t>(2 * u), w.k0, w.v0,
+                                   w.count, rocprim::maximum<double>(), rocprim::equal_to<uint64_t>(), s));
+    GNN_TRY(sync_read(w.count, &u, 1, s));
   } else {
-    e = hipMemsetAsync(w.count, 0, sizeof(int64_t), s);
-    if (e != hipSuccess) return static_cast<int>(e);
+    GNN_TRY(hipMemsetAsync(w.count, 0, sizeof(int64_t), s));
   }
   // + I (float64): diagonal keys appended, then one sorted sum
-  hipLaunchKernelGGL(append_diag_kernel, dim3(grid_for(n)), dim3(256), 0, s, w.k0, w.v0, w.count, n);
+  hipLaunchKernelGGL(append_diag_kernel, dim3(blocks(n, 256)), dim3(256), 0, s, w.k0, w.v0, w.count, n);
   tb = w.temp_bytes;
-  e = rocprim::radix_sort_pairs(w.temp, tb, w.k0, w.k1, w.v0, w.v1, static_cast<size_t>(u + n), 0,
-                                bits, s);
-  if (e != hipSuccess) return static_cast<int>(e);
+  GNN_TRY(rocprim::radix_sort_pairs(w.temp, tb, w.k0, w.k1, w.v0, w.v1, static_cast<size_t>(u + n), 0,
+                                    bits, s));
   tb = w.temp_bytes;
-  e = rocprim::deterministic_reduce_by_key(w.temp, tb, w.k1, w.v1, static_cast<size_t>(u + n), w.k0,
-                                           w.v0, w.count, rocprim::plus<double>(),
-                                           rocprim::equal_to<uint64_t>(), s);
-  if (e != hipSuccess) return static_cast<int>(e);
+  GNN_TRY(rocprim::deterministic_reduce_by_key(w.temp, tb, w.k1, w.v1, static_cast<size_t>(u + n), w.k0,
+                                               w.v0, w.count, rocprim::plus<double>(),
+                                               rocprim::equal_to<uint64_t>(), s));
   int64_t nnz = 0;
-  if ((rc = read_count(w.count, &nnz, s)) != GNN_OK) return rc;
+  GNN_TRY(sync_read(w.count, &nnz, 1, s));
   // rowsum per row (every row present: it holds its diagonal) -> d = rowsum^-1/2 in v1[0..n)
   auto rows = rocprim::make_transform_iterator(w.k0, RowOfKey{static_cast<uint64_t>(n)});
   tb = w.temp_bytes;
-  e = rocprim::deterministic_reduce_by_key(w.temp, tb, rows, w.v0, static_cast<size_t>(nnz), w.k1,
-                                           w.v1, w.count + 1, rocprim::plus<double>(),
-                                           rocprim::equal_to<uint64_t>(), s);
-  if (e != hipSuccess) return static_cast<int>(e);
-  hipLaunchKernelGGL(inv_sqrt_kernel, dim3(grid_for(n)), dim3(256), 0, s, w.v1, n);
+  GNN_TRY(rocprim::deterministic_reduce_by_key(w.temp, tb, rows, w.v0, static_cast<size_t>(nnz), w.k1,
+                                               w.v1, w.count + 1, rocprim::plus<double>(),
+                                               rocprim::equal_to<uint64_t>(), s));
+  hipLaunchKernelGGL(inv_sqrt_kernel, dim3(blocks(n, 256)), dim3(256), 0, s, w.v1, n);
   // transpose + normalise, then sort by the new (row, col)
-  hipLaunchKernelGGL(normalise_transpose_kernel, dim3(grid_for(nnz)), dim3(256), 0, s, w.k0, w.v0,
+  hipLaunchKernelGGL(normalise_transpose_kernel, dim3(blocks(nnz, 256)), dim3(256), 0, s, w.k0, w.v0,
                      w.v1, w.k1, w.count, n);
   tb = w.temp_bytes;
-  e = rocprim::radix_sort_pairs(w.temp, tb, w.k1, w.k0, w.v0, w.v1, static_cast<size_t>(nnz), 0,
-                                bits, s);
-  if (e != hipSuccess) return static_cast<int>(e);
+  GNN_TRY(rocprim::radix_sort_pairs(w.temp, tb, w.k1, w.k0, w.v0, w.v1, static_cast<size_t>(nnz), 0,
+                                    bits, s));
   *nnz_out = nnz;
   return launch_status();
 }
@@ -286,7 +259,7 @@ extern "C" int gnn_gcn_adjacency_fill(const void* workspace, int64_t n_edges, in
                                       void* stream) {
   if (!workspace || n_nodes < 1 || nnz < n_nodes || !rowptr || !col || !val) return GNN_E_ARG;
   BuildWs w = carve(const_cast<void*>(workspace), n_edges, n_nodes);
-  hipLaunchKernelGGL(emit_csr_kernel, dim3(grid_for(nnz)), dim3(256), 0,
+  hipLaunchKernelGGL(emit_csr_kernel, dim3(blocks(nnz, 256)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), w.k0, w.v1, nnz, n_nodes, rowptr, col, val);
   return launch_status();
 }

@@ -12,6 +12,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "common.hpp"
+#include "host.hpp"
 
 namespace gnn {
 
@@ -78,13 +79,6 @@ __global__ void hub_rename_kernel(const int32_t* __restrict__ col, int64_t nnz,
   }
 }
 
-static unsigned grid_for_n(int64_t n) {
-  const int64_t b = (n + 255) / 256;
-  return static_cast<unsigned>(b < 1 ? 1 : (b > 65536 ? 65536 : b));
-}
-
-static int64_t align256(int64_t v) { return (v + 255) / 256 * 256; }
-
 static size_t hub_sort_temp_bytes(int64_t n_cols) {
   size_t t = 0;
   (void)rocprim::radix_sort_pairs(nullptr, t, static_cast<uint32_t*>(nullptr),
@@ -93,14 +87,41 @@ static size_t hub_sort_temp_bytes(int64_t n_cols) {
   return t;
 }
 
+struct HubWs {
+  uint32_t* deg;      // [n] in-degrees, then the sort keys ~deg
+  uint32_t* key_out;  // [n]
+  int32_t* id_in;     // [n]
+  int32_t* id_out;    // [n] columns by descending degree
+  int32_t* rank;      // [n] hub rank of a column, -1 for the others
+  void* temp;
+  size_t temp_bytes;
+  int64_t bytes;
+};
+
+static HubWs hub_carve(void* ws, int64_t n_cols) {
+  Carve c{static_cast<char*>(ws)};
+  HubWs w{};
+  const int64_t n = n_cols > 0 ? n_cols : 1;
+  w.deg = c.take<uint32_t>(n);
+  w.key_out = c.take<uint32_t>(n);
+  w.id_in = c.take<int32_t>(n);
+  w.id_out = c.take<int32_t>(n);
+  w.rank = c.take<int32_t>(n);
+  c.raw(256);
+  w.temp_bytes = hub_sort_temp_bytes(n);
+  w.temp = c.raw(static_cast<int64_t>(w.temp_bytes));
+  c.raw(256);
+  w.bytes = c.used;
+  return w;
+}
+
 }  // namespace gnn
 
 using namespace gnn;
 
 extern "C" int64_t gnn_hub_plan_workspace_bytes(int64_t n_cols) {
   if (n_cols < 0) return GNN_E_ARG;
-  const int64_t n = n_cols > 0 ? n_cols : 1;
-  return 5 * align256(4 * n) + 256 + static_cast<int64_t>(hub_sort_temp_bytes(n)) + 256;
+  return hub_carve(nullptr, n_cols).bytes;
 }
 
 extern "C" int gnn_hub_plan_build(const int32_t* col, int64_t nnz, int64_t n_cols, int64_t k,
@@ -110,33 +131,24 @@ extern "C" int gnn_hub_plan_build(const int32_t* col, int64_t nnz, int64_t n_col
       (nnz > 0 && (!col || !col_hub)))
     return GNN_E_ARG;
   if (n_cols > 0x7fffffffLL) return GNN_E_UNSUPPORTED;
-  if (workspace_bytes < gnn_hub_plan_workspace_bytes(n_cols)) return GNN_E_ARG;
+  HubWs w = hub_carve(workspace, n_cols);
+  if (workspace_bytes < w.bytes) return GNN_E_ARG;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  char* p = static_cast<char*>(workspace);
-  const int64_t seg = align256(4 * n_cols);
-  uint32_t* deg = reinterpret_cast<uint32_t*>(p);
-  uint32_t* key_out = reinterpret_cast<uint32_t*>(p + seg);
-  int32_t* id_in = reinterpret_cast<int32_t*>(p + 2 * seg);
-  int32_t* id_out = reinterpret_cast<int32_t*>(p + 3 * seg);
-  int32_t* rank = reinterpret_cast<int32_t*>(p + 4 * seg);
-  void* temp = p + 5 * seg + 256;
-  size_t tb = static_cast<size_t>(workspace_bytes - (5 * seg + 256));
-  hipError_t e = hipMemsetAsync(deg, 0, 4 * n_cols, s);
-  if (e != hipSuccess) return static_cast<int>(e);
+  size_t tb = w.temp_bytes;
+  GNN_TRY(hipMemsetAsync(w.deg, 0, 4 * n_cols, s));
   if (nnz > 0)
     hipLaunchKernelGGL(hub_degree_kernel,
-                       dim3(grid_for_n(nnz) < kHubDegBlocks ? grid_for_n(nnz) : kHubDegBlocks),
-                       dim3(256), 0, s, col, nnz, n_cols, deg, err_flag);
-  hipLaunchKernelGGL(hub_keys_kernel, dim3(grid_for_n(n_cols)), dim3(256), 0, s, deg, n_cols,
-                     id_in, rank);
-  e = rocprim::radix_sort_pairs(temp, tb, deg, key_out, id_in, id_out,
-                                static_cast<size_t>(n_cols), 0, 32, s);
-  if (e != hipSuccess) return static_cast<int>(e);
-  hipLaunchKernelGGL(hub_rank_kernel, dim3(grid_for_n(k)), dim3(256), 0, s, id_out, k, hub_ids,
-                     rank);
+                       dim3(blocks_capped(nnz) < kHubDegBlocks ? blocks_capped(nnz) : kHubDegBlocks),
+                       dim3(256), 0, s, col, nnz, n_cols, w.deg, err_flag);
+  hipLaunchKernelGGL(hub_keys_kernel, dim3(blocks_capped(n_cols)), dim3(256), 0, s, w.deg, n_cols,
+                     w.id_in, w.rank);
+  GNN_TRY(rocprim::radix_sort_pairs(w.temp, tb, w.deg, w.key_out, w.id_in, w.id_out,
+                                    static_cast<size_t>(n_cols), 0, 32, s));
+  hipLaunchKernelGGL(hub_rank_kernel, dim3(blocks_capped(k)), dim3(256), 0, s, w.id_out, k, hub_ids,
+                     w.rank);
   if (nnz > 0)
-    hipLaunchKernelGGL(hub_rename_kernel, dim3(grid_for_n(nnz)), dim3(256), 0, s, col, nnz, rank,
-                       n_cols, col_hub);
+    hipLaunchKernelGGL(hub_rename_kernel, dim3(blocks_capped(nnz)), dim3(256), 0, s, col, nnz,
+                       w.rank, n_cols, col_hub);
   return launch_status();
 }
 
@@ -144,11 +156,10 @@ extern "C" int gnn_in_degree_u32(const int32_t* col, int64_t nnz, int64_t n_cols
                                  int32_t* err_flag, void* stream) {
   if (nnz < 0 || n_cols < 1 || !deg || !err_flag || (nnz > 0 && !col)) return GNN_E_ARG;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  hipError_t e = hipMemsetAsync(deg, 0, 4 * n_cols, s);
-  if (e != hipSuccess) return static_cast<int>(e);
+  GNN_TRY(hipMemsetAsync(deg, 0, 4 * n_cols, s));
   if (nnz > 0)
     hipLaunchKernelGGL(hub_degree_kernel,
-                       dim3(grid_for_n(nnz) < kHubDegBlocks ? grid_for_n(nnz) : kHubDegBlocks),
+                       dim3(blocks_capped(nnz) < kHubDegBlocks ? blocks_capped(nnz) : kHubDegBlocks),
                        dim3(256), 0, s, col, nnz, n_cols, deg, err_flag);
   return launch_status();
 }

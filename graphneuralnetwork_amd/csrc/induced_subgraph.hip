@@ -32,6 +32,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "common.hpp"
+#include "host.hpp"
 
 namespace gnn {
 
@@ -47,8 +48,6 @@ constexpr int kIsHeavyGridWs = 64;     // ... bitmaps in the workspace (a fixed 
 constexpr int64_t kIsDimLimit = 0x7fffffffLL;  // n, b below 2^31 - 1
 constexpr int kIsBadIdx = 1, kIsBadGraph = 2, kIsRepeat = 4;  // status bits 0, 1, 2
 constexpr unsigned long long kIsNoKey = ~0ull;
-
-static int64_t is_align(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
 
 static size_t is_temp_bytes(int64_t b) {
   size_t need = 0;
@@ -75,36 +74,25 @@ struct IsWs {
   unsigned long long* bitmap;  // [kIsHeavyGridWs][words], only above kIsLdsBits
   uint32_t* prefix;            // [kIsHeavyGridWs][words]
   int64_t words;               // per bitmap, padded to 256 B
-  int64_t total;
+  int64_t bytes;
 };
 
 static IsWs is_carve(void* ws, int64_t n, int64_t b) {
+  Carve c{static_cast<char*>(ws)};
   IsWs w{};
-  char* p = static_cast<char*>(ws);
-  char* const p0 = p;
-  w.head = reinterpret_cast<int32_t*>(p);
-  p += is_align(n * 4, 256);
-  w.next = reinterpret_cast<int32_t*>(p);
-  p += is_align(b * 4, 256);
-  w.clen = reinterpret_cast<int32_t*>(p);
-  p += is_align(b * 4, 256);
-  w.cnt = reinterpret_cast<int64_t*>(p);
-  p += is_align((b + 1) * 8, 256);
-  w.mid_row = reinterpret_cast<int32_t*>(p);
-  p += is_align(b * 4, 256);
-  w.heavy_row = reinterpret_cast<int32_t*>(p);
-  p += is_align(b * 4, 256);
-  w.n_class = reinterpret_cast<int32_t*>(p);
-  p += 256;
-  w.temp = p;
+  w.head = c.take<int32_t>(n);
+  w.next = c.take<int32_t>(b);
+  w.clen = c.take<int32_t>(b);
+  w.cnt = c.take<int64_t>(b + 1);
+  w.mid_row = c.take<int32_t>(b);
+  w.heavy_row = c.take<int32_t>(b);
+  w.n_class = c.take<int32_t>(2);
   w.temp_bytes = is_temp_bytes(b);
-  p += is_align(static_cast<int64_t>(w.temp_bytes), 256);
-  w.words = b > kIsLdsBits ? is_align((b + 63) / 64 * 8, 256) / 8 : 0;
-  w.bitmap = reinterpret_cast<unsigned long long*>(p);
-  p += w.words * 8 * kIsHeavyGridWs;
-  w.prefix = reinterpret_cast<uint32_t*>(p);
-  p += w.words * 4 * kIsHeavyGridWs;
-  w.total = p - p0;
+  w.temp = c.take<char>(static_cast<int64_t>(w.temp_bytes));
+  w.words = b > kIsLdsBits ? up256((b + 63) / 64 * 8) / 8 : 0;
+  w.bitmap = c.take<unsigned long long>(w.words * kIsHeavyGridWs);
+  w.prefix = c.take<uint32_t>(w.words * kIsHeavyGridWs);
+  w.bytes = c.used;
   return w;
 }
 
@@ -500,10 +488,6 @@ __global__ __launch_bounds__(kIsBlock) void is_heavy_kernel(
   }
 }
 
-static inline unsigned is_grid(int64_t n, int per) {
-  return static_cast<unsigned>((n + per - 1) / per);
-}
-
 static int is_check_dims(int64_t n, int64_t b) {
   if (n < 0 || b < 0) return GNN_E_ARG;
   if (n >= kIsDimLimit || b >= kIsDimLimit) return GNN_E_UNSUPPORTED;
@@ -515,7 +499,7 @@ static void is_launch_fill(const int64_t* rowptr, const int32_t* col, const floa
                            int64_t n, const int64_t* idx, int64_t b, const IsWs& w,
                            const int64_t* crp, int32_t* ccol, float* cval, int64_t nnz_c,
                            int32_t* status, hipStream_t s) {
-  hipLaunchKernelGGL(is_short_kernel<VAL>, dim3(is_grid(b, kIsWaves)), dim3(kIsBlock), 0, s, rowptr,
+  hipLaunchKernelGGL(is_short_kernel<VAL>, dim3(blocks(b, kIsWaves)), dim3(kIsBlock), 0, s, rowptr,
                      col, val, nnz, n, idx, b, w.head, w.next, w.clen, crp, ccol, cval, nnz_c,
                      w.mid_row, w.heavy_row, w.n_class, status);
   const int64_t mid_grid = b < kIsMidGrid ? b : kIsMidGrid;
@@ -544,7 +528,7 @@ extern "C" int64_t gnn_induced_subgraph_workspace_bytes(int64_t n, int64_t b) {
   if (rc != GNN_OK) return rc;
   // the terms: the map (4 n + 8 b), O(b) row arrays and rocPRIM's temporaries, and above
   // kIsLdsBits a fixed number of b-bit bitmaps with their word prefixes
-  return is_carve(nullptr, n, b).total + 256;
+  return is_carve(nullptr, n, b).bytes + 256;
 }
 
 extern "C" int gnn_induced_subgraph_class_limits(int64_t* short_max, int64_t* mid_max,
@@ -561,17 +545,14 @@ extern "C" int gnn_induced_subgraph_map(const int64_t* idx, int64_t b, int64_t n
   const int rc = is_check_dims(n, b);
   if (rc != GNN_OK) return rc;
   if (!status || !workspace || (b > 0 && !idx)) return GNN_E_ARG;
-  if (workspace_bytes < gnn_induced_subgraph_workspace_bytes(n, b)) return GNN_E_ARG;
-  hipStream_t s = static_cast<hipStream_t>(stream);
   IsWs w = is_carve(workspace, n, b);
-  if (n > 0) {
-    const hipError_t e = hipMemsetAsync(w.head, 0xff, static_cast<size_t>(n) * 4, s);  // all -1
-    if (e != hipSuccess) return static_cast<int>(e);
-  }
+  if (workspace_bytes < w.bytes + 256) return GNN_E_ARG;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (n > 0) GNN_TRY(hipMemsetAsync(w.head, 0xff, static_cast<size_t>(n) * 4, s));  // all -1
   if (b > 0) {
-    hipLaunchKernelGGL(is_map_push_kernel, dim3(is_grid(b, 256)), dim3(256), 0, s, idx, b, n,
+    hipLaunchKernelGGL(is_map_push_kernel, dim3(blocks(b, 256)), dim3(256), 0, s, idx, b, n,
                        w.head, w.next, status);
-    hipLaunchKernelGGL(is_map_len_kernel, dim3(is_grid(b, 256)), dim3(256), 0, s, idx, b, n, w.head,
+    hipLaunchKernelGGL(is_map_len_kernel, dim3(blocks(b, 256)), dim3(256), 0, s, idx, b, n, w.head,
                        w.next, w.clen);
   }
   return launch_status();
@@ -586,20 +567,18 @@ extern "C" int gnn_induced_subgraph_count(const int64_t* rowptr, const int32_t* 
   if (nnz < 0 || !rowptr || !c_rowptr || !status || !workspace || (nnz > 0 && !col) ||
       (b > 0 && !idx))
     return GNN_E_ARG;
-  if (workspace_bytes < gnn_induced_subgraph_workspace_bytes(n, b)) return GNN_E_ARG;
+  IsWs w = is_carve(workspace, n, b);
+  if (workspace_bytes < w.bytes + 256) return GNN_E_ARG;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (b == 0) {
-    const hipError_t e = hipMemsetAsync(c_rowptr, 0, sizeof(int64_t), s);
-    return e == hipSuccess ? launch_status() : static_cast<int>(e);
+    GNN_TRY(hipMemsetAsync(c_rowptr, 0, sizeof(int64_t), s));
+    return launch_status();
   }
-  IsWs w = is_carve(workspace, n, b);
-  hipLaunchKernelGGL(is_count_kernel, dim3(is_grid(b, kIsWaves)), dim3(kIsBlock), 0, s, rowptr, col,
+  hipLaunchKernelGGL(is_count_kernel, dim3(blocks(b, kIsWaves)), dim3(kIsBlock), 0, s, rowptr, col,
                      nnz, n, idx, b, w.head, w.clen, w.cnt, status);
   size_t tb = w.temp_bytes;
-  const hipError_t e =
-      rocprim::exclusive_scan(w.temp, tb, w.cnt, c_rowptr, static_cast<int64_t>(0),
-                              static_cast<size_t>(b + 1), rocprim::plus<int64_t>(), s);
-  if (e != hipSuccess) return static_cast<int>(e);
+  GNN_TRY(rocprim::exclusive_scan(w.temp, tb, w.cnt, c_rowptr, static_cast<int64_t>(0),
+                                  static_cast<size_t>(b + 1), rocprim::plus<int64_t>(), s));
   return launch_status();
 }
 
@@ -614,12 +593,11 @@ extern "C" int gnn_induced_subgraph_fill(const int64_t* rowptr, const int32_t* c
   if (nnz < 0 || nnz_c < 0 || !rowptr || !c_rowptr || !status || !workspace ||
       (nnz > 0 && !col) || (b > 0 && !idx) || (nnz_c > 0 && !c_col))
     return GNN_E_ARG;
-  if (workspace_bytes < gnn_induced_subgraph_workspace_bytes(n, b)) return GNN_E_ARG;
+  IsWs w = is_carve(workspace, n, b);
+  if (workspace_bytes < w.bytes + 256) return GNN_E_ARG;
   if (nnz_c == 0 || b == 0) return GNN_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  IsWs w = is_carve(workspace, n, b);
-  const hipError_t e = hipMemsetAsync(w.n_class, 0, 2 * sizeof(int32_t), s);
-  if (e != hipSuccess) return static_cast<int>(e);
+  GNN_TRY(hipMemsetAsync(w.n_class, 0, 2 * sizeof(int32_t), s));
   if (val && c_val)
     is_launch_fill<true>(rowptr, col, val, nnz, n, idx, b, w, c_rowptr, c_col, c_val, nnz_c, status,
                          s);

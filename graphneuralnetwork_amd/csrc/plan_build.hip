@@ -14,6 +14,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "common.hpp"
+#include "host.hpp"
 
 extern "C" int gnn_in_degree_u32(const int32_t* col, int64_t nnz, int64_t n_cols, uint32_t* deg,
                                  int32_t* err_flag, void* stream);
@@ -35,31 +36,11 @@ constexpr int64_t kMaxSlices = 1024;
 #endif
 constexpr int64_t kSliceGroup = GNN_XCD_SLICE_GROUP;
 
-static inline unsigned grid(int64_t n) { return static_cast<unsigned>((n + kT - 1) / kT); }
-static inline int64_t up(int64_t v) { return (v + 255) / 256 * 256; }
-
 static unsigned bits_for(uint64_t max_value) {  // bits to hold values < max_value
   unsigned b = 1;
   while (b < 64 && (static_cast<uint64_t>(1) << b) < max_value) ++b;
   return b;
 }
-
-static int sync_read(const int64_t* dev, int64_t* host, int64_t count, hipStream_t s) {
-  hipError_t e = hipMemcpyAsync(host, dev, count * sizeof(int64_t), hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  return e == hipSuccess ? GNN_OK : static_cast<int>(e);
-}
-
-// bump allocator over the caller's workspace (256-byte aligned pieces)
-struct Carve {
-  char* p;
-  int64_t used = 0;
-  template <class T> T* take(int64_t n) {
-    T* r = reinterpret_cast<T*>(p ? p + used : nullptr);
-    used += up(n * static_cast<int64_t>(sizeof(T)));
-    return r;
-  }
-};
 
 typedef rocprim::counting_iterator<int64_t> Count;
 
@@ -608,12 +589,6 @@ static XcdWs xcd_carve(void* ws, int64_t E, int64_t N) {
   return w;
 }
 
-#define PB_TRY(x)                                       \
-  do {                                                  \
-    hipError_t e_ = (x);                                \
-    if (e_ != hipSuccess) return static_cast<int>(e_);  \
-  } while (0)
-
 }  // namespace pb
 }  // namespace gnn
 
@@ -635,34 +610,33 @@ extern "C" int gnn_spmm_tasks_build(const int64_t* rowptr, int64_t n_rows, int64
   if (n_rows > 0x7fffffffLL) return GNN_E_UNSUPPORTED;  // int32 task bounds
   *n_task = 0;
   if (n_rows == 0) return GNN_OK;
-  if (workspace_bytes < gnn_spmm_tasks_workspace_bytes(n_rows)) return GNN_E_ARG;
-  hipStream_t s = static_cast<hipStream_t>(stream);
   TaskWs w = task_carve(workspace, n_rows);
+  if (workspace_bytes < w.bytes) return GNN_E_ARG;
+  hipStream_t s = static_cast<hipStream_t>(stream);
   const size_t n = static_cast<size_t>(n_rows);
   size_t tb = w.temp_bytes;
   const auto cost_it = rocprim::make_transform_iterator(Count(0), TaskCost{rowptr, n_rows, max_deg});
-  PB_TRY(rocprim::exclusive_scan(w.temp, tb, cost_it, w.excl, int64_t(0), n, rocprim::plus<int64_t>(), s));
+  GNN_TRY(rocprim::exclusive_scan(w.temp, tb, cost_it, w.excl, int64_t(0), n, rocprim::plus<int64_t>(), s));
   tb = w.temp_bytes;
   const auto head_it = rocprim::make_transform_iterator(Count(0), RunHead{rowptr, max_deg});
-  PB_TRY(rocprim::inclusive_scan(w.temp, tb, head_it, w.first, n, rocprim::maximum<int64_t>(), s));
-  hipLaunchKernelGGL(task_flags_kernel, dim3(grid(n_rows)), dim3(kT), 0, s, rowptr, n_rows, max_deg,
+  GNN_TRY(rocprim::inclusive_scan(w.temp, tb, head_it, w.first, n, rocprim::maximum<int64_t>(), s));
+  hipLaunchKernelGGL(task_flags_kernel, dim3(blocks(n_rows, kT)), dim3(kT), 0, s, rowptr, n_rows, max_deg,
                      cost, w.excl, w.first, w.flags);
   tb = w.temp_bytes;
   const auto flag_it = rocprim::make_transform_iterator(Count(0), Bit0{w.flags});
-  PB_TRY(rocprim::select(w.temp, tb, Count(0), flag_it, w.bounds, w.cnt, n, s));
-  hipLaunchKernelGGL(task_pairs_kernel, dim3(grid(n_rows)), dim3(kT), 0, s, w.bounds, w.cnt, w.flags,
+  GNN_TRY(rocprim::select(w.temp, tb, Count(0), flag_it, w.bounds, w.cnt, n, s));
+  hipLaunchKernelGGL(task_pairs_kernel, dim3(blocks(n_rows, kT)), dim3(kT), 0, s, w.bounds, w.cnt, w.flags,
                      n_rows, w.pairs);
   tb = w.temp_bytes;
-  PB_TRY(rocprim::select(w.temp, tb, w.pairs, reinterpret_cast<uint64_t*>(w.excl), w.cnt + 1, n,
+  GNN_TRY(rocprim::select(w.temp, tb, w.pairs, reinterpret_cast<uint64_t*>(w.excl), w.cnt + 1, n,
                          NotSentinel{}, s));
   int64_t nt = 0;
-  int rc = sync_read(w.cnt + 1, &nt, 1, s);
-  if (rc != GNN_OK) return rc;
+  GNN_TRY(sync_read(w.cnt + 1, &nt, 1, s));
   *n_task = nt;
   if (!task_row) return launch_status();
   if (nt > cap_tasks) return GNN_E_ARG;  // *n_task says how many pairs to make room for
   if (nt > 0)
-    PB_TRY(hipMemcpyAsync(task_row, w.excl, static_cast<size_t>(nt) * 8, hipMemcpyDeviceToDevice, s));
+    GNN_TRY(hipMemcpyAsync(task_row, w.excl, static_cast<size_t>(nt) * 8, hipMemcpyDeviceToDevice, s));
   return launch_status();
 }
 
@@ -678,35 +652,33 @@ extern "C" int gnn_column_order(const int32_t* col, int64_t nnz, int64_t n_cols,
   if (nnz < 0 || n_cols < 1 || !perm || !inv || !workspace || (nnz > 0 && (!col || !col_out)))
     return GNN_E_ARG;
   if (n_cols > 0x7fffffffLL) return GNN_E_UNSUPPORTED;  // int32 column ids
-  if (workspace_bytes < gnn_column_order_workspace_bytes(n_cols)) return GNN_E_ARG;
-  hipStream_t s = static_cast<hipStream_t>(stream);
   OrderWs w = order_carve(workspace, n_cols);
-  PB_TRY(hipMemsetAsync(w.err, 0, sizeof(int32_t), s));
-  if (nnz == 0) PB_TRY(hipMemsetAsync(w.deg, 0, static_cast<size_t>(n_cols) * 4, s));
+  if (workspace_bytes < w.bytes) return GNN_E_ARG;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  GNN_TRY(hipMemsetAsync(w.err, 0, sizeof(int32_t), s));
+  if (nnz == 0) GNN_TRY(hipMemsetAsync(w.deg, 0, static_cast<size_t>(n_cols) * 4, s));
   if (nnz > 0) {
-    const int rc = gnn_in_degree_u32(col, nnz, n_cols, w.deg, w.err, stream);
-    if (rc != GNN_OK) return rc;
-    int64_t herr = 0;
-    PB_TRY(hipMemcpyAsync(&herr, w.err, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    PB_TRY(hipStreamSynchronize(s));
+    GNN_TRY(gnn_in_degree_u32(col, nnz, n_cols, w.deg, w.err, stream));
+    int32_t herr = 0;
+    GNN_TRY(sync_read(w.err, &herr, 1, s));
     if (herr) return GNN_E_ARG;  // a column id outside [0, n_cols)
   }
   const size_t n = static_cast<size_t>(n_cols);
-  hipLaunchKernelGGL(order_keys_kernel, dim3(grid(n_cols)), dim3(kT), 0, s, w.deg, n_cols, w.key0, w.ids);
+  hipLaunchKernelGGL(order_keys_kernel, dim3(blocks(n_cols, kT)), dim3(kT), 0, s, w.deg, n_cols, w.key0, w.ids);
   size_t tb = w.temp_bytes;
-  PB_TRY(rocprim::radix_sort_pairs(w.temp, tb, w.key0, w.key1, w.ids, perm, n, 0, 32, s));
+  GNN_TRY(rocprim::radix_sort_pairs(w.temp, tb, w.key0, w.key1, w.ids, perm, n, 0, 32, s));
   if (prefix >= 0 && prefix < n_cols) {
     // the ids after the prefix in ascending order (graph.degree_order's default tail)
-    PB_TRY(hipMemsetAsync(w.mark, 0, n, s));
+    GNN_TRY(hipMemsetAsync(w.mark, 0, n, s));
     if (prefix > 0)
-      hipLaunchKernelGGL(order_mark_kernel, dim3(grid(prefix)), dim3(kT), 0, s, perm, prefix, w.mark);
+      hipLaunchKernelGGL(order_mark_kernel, dim3(blocks(prefix, kT)), dim3(kT), 0, s, perm, prefix, w.mark);
     tb = w.temp_bytes;
     const auto keep_it = rocprim::make_transform_iterator(Count(0), NotMarked{w.mark});
-    PB_TRY(rocprim::select(w.temp, tb, Count(0), keep_it, perm + prefix, w.cnt, n, s));
+    GNN_TRY(rocprim::select(w.temp, tb, Count(0), keep_it, perm + prefix, w.cnt, n, s));
   }
-  hipLaunchKernelGGL(order_inv_kernel, dim3(grid(n_cols)), dim3(kT), 0, s, perm, n_cols, inv);
+  hipLaunchKernelGGL(order_inv_kernel, dim3(blocks(n_cols, kT)), dim3(kT), 0, s, perm, n_cols, inv);
   if (nnz > 0)
-    hipLaunchKernelGGL(order_rename_kernel, dim3(grid(nnz)), dim3(kT), 0, s, col, nnz, inv, col_out);
+    hipLaunchKernelGGL(order_rename_kernel, dim3(blocks(nnz, kT)), dim3(kT), 0, s, col, nnz, inv, col_out);
   return launch_status();
 }
 
@@ -732,79 +704,78 @@ extern "C" int gnn_xcd_hub_plan_build(const int64_t* rowptr, const int32_t* col_
   if (chunk < 4 || phases < 1 || S > kMaxSlices || k < S || ik < S || (small_item != 0 && small_item < 2))
     return GNN_E_ARG;  // graph.xcd_hub_coo's ValueErrors
   if (n_rows > 0x7fffffffLL || nnz > 0xffffffffLL) return GNN_E_UNSUPPORTED;
-  if (workspace_bytes < gnn_xcd_hub_plan_workspace_bytes(n_rows, nnz)) return GNN_E_ARG;
+  XcdWs w = xcd_carve(workspace, nnz, n_rows);
+  if (workspace_bytes < w.bytes) return GNN_E_ARG;
   for (int i = 0; i < 4; ++i) counts[i] = 0;
   if (nnz == 0) return GNN_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  XcdWs w = xcd_carve(workspace, nnz, n_rows);
-  PB_TRY(hipMemsetAsync(w.hdr, 0, (16 + kMaxSlices) * sizeof(int64_t), s));
+  GNN_TRY(hipMemsetAsync(w.hdr, 0, (16 + kMaxSlices) * sizeof(int64_t), s));
   const int64_t gsz = kSliceGroup > 1 && ik >= S * kSliceGroup ? kSliceGroup : 1;
   hipLaunchKernelGGL(xcd_group_kernel, dim3(1), dim3(64), 0, s, w.hdr, gsz);
-  hipLaunchKernelGGL(edge_row_kernel, dim3(grid(nnz)), dim3(kT), 0, s, rowptr, n_rows, nnz, w.row_e);
+  hipLaunchKernelGGL(edge_row_kernel, dim3(blocks(nnz, kT)), dim3(kT), 0, s, rowptr, n_rows, nnz, w.row_e);
   // 1. the hub edges that may form items, by (row, slice), CSR order kept inside a group
   size_t tb = w.temp_bytes;
   const auto elig_it = rocprim::make_transform_iterator(
       Count(0), EligOp{rowptr, col_hub, w.row_e, ik, small_item > 0 ? 2 : min_deg});
-  PB_TRY(rocprim::select(w.temp, tb, Count(0), elig_it, w.eid0, w.hdr, static_cast<size_t>(nnz), s));
+  GNN_TRY(rocprim::select(w.temp, tb, Count(0), elig_it, w.eid0, w.hdr, static_cast<size_t>(nnz), s));
   int64_t n_sel = 0;
-  int rc = sync_read(w.hdr, &n_sel, 1, s);
-  if (rc != GNN_OK) return rc;
+  GNN_TRY(sync_read(w.hdr, &n_sel, 1, s));
   if (n_sel == 0) return launch_status();
-  hipLaunchKernelGGL(xcd_keys_kernel, dim3(grid(n_sel)), dim3(kT), 0, s, w.eid0, w.hdr, col_hub,
+  hipLaunchKernelGGL(xcd_keys_kernel, dim3(blocks(n_sel, kT)), dim3(kT), 0, s, w.eid0, w.hdr, col_hub,
                      w.row_e, S, w.key0);
   tb = w.temp_bytes;
   const unsigned kbits = bits_for(static_cast<uint64_t>(n_rows) * static_cast<uint64_t>(S));
-  PB_TRY(rocprim::radix_sort_pairs(w.temp, tb, w.key0, w.key1, w.eid0, w.eid1,
+  GNN_TRY(rocprim::radix_sort_pairs(w.temp, tb, w.key0, w.key1, w.eid0, w.eid1,
                                    static_cast<size_t>(n_sel), 0, kbits, s));
   // 2. groups = (row, slice) runs; moved groups of >= 2 edges are cut into balanced chunks
   tb = w.temp_bytes;
-  PB_TRY(rocprim::run_length_encode(w.temp, tb, w.key1, static_cast<unsigned int>(n_sel), w.key0,
+  GNN_TRY(rocprim::run_length_encode(w.temp, tb, w.key1, static_cast<unsigned int>(n_sel), w.key0,
                                     w.gcnt, w.hdr + 1, s));
   int64_t G = 0;
-  if ((rc = sync_read(w.hdr + 1, &G, 1, s)) != GNN_OK) return rc;
-  hipLaunchKernelGGL(xcd_groups_kernel, dim3(grid(G)), dim3(kT), 0, s, w.key0, w.gcnt, G, rowptr, S,
+  GNN_TRY(sync_read(w.hdr + 1, &G, 1, s));
+  hipLaunchKernelGGL(xcd_groups_kernel, dim3(blocks(G, kT)), dim3(kT), 0, s, w.key0, w.gcnt, G, rowptr, S,
                      min_deg, small_item, chunk, w.nch, w.hdr);
   tb = w.temp_bytes;
   const auto gc_it = rocprim::make_transform_iterator(Count(0), GroupCount{w.gcnt, G});
-  PB_TRY(rocprim::exclusive_scan(w.temp, tb, gc_it, w.gstart, int64_t(0), static_cast<size_t>(G + 1),
+  GNN_TRY(rocprim::exclusive_scan(w.temp, tb, gc_it, w.gstart, int64_t(0), static_cast<size_t>(G + 1),
                                  rocprim::plus<int64_t>(), s));
   tb = w.temp_bytes;
   const auto nch_it = rocprim::make_transform_iterator(Count(0), Arr64{w.nch, G});
-  PB_TRY(rocprim::exclusive_scan(w.temp, tb, nch_it, w.ibase, int64_t(0), static_cast<size_t>(G + 1),
+  GNN_TRY(rocprim::exclusive_scan(w.temp, tb, nch_it, w.ibase, int64_t(0), static_cast<size_t>(G + 1),
                                  rocprim::plus<int64_t>(), s));
-  PB_TRY(hipMemcpyAsync(w.hdr + 2, w.ibase + G, sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+  GNN_TRY(hipMemcpyAsync(w.hdr + 2, w.ibase + G, sizeof(int64_t), hipMemcpyDeviceToDevice, s));
   int64_t h[4];
-  if ((rc = sync_read(w.hdr, h, 4, s)) != GNN_OK) return rc;
+  GNN_TRY(sync_read(w.hdr, h, 4, s));
   const int64_t I = h[2], n_moved = h[3];
   if (I == 0) return launch_status();  // no row has two hub edges in one slice
   // 3. items: slice, row, edge range; per-row deltas; moved-edge marks
-  PB_TRY(hipMemsetAsync(w.row_delta, 0, static_cast<size_t>(n_rows) * 8, s));
-  hipLaunchKernelGGL(xcd_items_kernel, dim3(grid(G)), dim3(kT), 0, s, w.key0, w.gcnt, G, S, w.nch,
+  GNN_TRY(hipMemsetAsync(w.row_delta, 0, static_cast<size_t>(n_rows) * 8, s));
+  hipLaunchKernelGGL(xcd_items_kernel, dim3(blocks(G, kT)), dim3(kT), 0, s, w.key0, w.gcnt, G, S, w.nch,
                      w.ibase, w.gstart, w.it_slice, w.it_row, w.it_e0, w.it_cnt, w.row_delta);
-  PB_TRY(hipMemsetAsync(w.moved_e, 0, static_cast<size_t>(nnz), s));
-  hipLaunchKernelGGL(xcd_moved_kernel, dim3(grid(n_sel)), dim3(kT), 0, s, w.eid1, n_sel, w.gstart,
+  GNN_TRY(hipMemsetAsync(w.moved_e, 0, static_cast<size_t>(nnz), s));
+  hipLaunchKernelGGL(xcd_moved_kernel, dim3(blocks(n_sel, kT)), dim3(kT), 0, s, w.eid1, n_sel, w.gstart,
                      w.nch, G, w.moved_e);
   // 4. rank of each item inside its slice (stable: item order), positions per phase
-  hipLaunchKernelGGL(iota_kernel, dim3(grid(I)), dim3(kT), 0, s, w.it_idx0, I);
+  hipLaunchKernelGGL(iota_kernel, dim3(blocks(I, kT)), dim3(kT), 0, s, w.it_idx0, I);
   tb = w.temp_bytes;
-  PB_TRY(rocprim::radix_sort_pairs(w.temp, tb, w.it_slice, w.it_slice2, w.it_idx0, w.it_idx1,
+  GNN_TRY(rocprim::radix_sort_pairs(w.temp, tb, w.it_slice, w.it_slice2, w.it_idx0, w.it_idx1,
                                    static_cast<size_t>(I), 0, bits_for(static_cast<uint64_t>(S)), s));
-  PB_TRY(hipMemsetAsync(w.cstart, 0, kMaxSlices * 8, s));
-  PB_TRY(hipMemsetAsync(w.cend, 0, kMaxSlices * 8, s));
-  hipLaunchKernelGGL(xcd_slice_bounds_kernel, dim3(grid(I)), dim3(kT), 0, s, w.it_slice2, I, w.cstart,
+  GNN_TRY(hipMemsetAsync(w.cstart, 0, kMaxSlices * 8, s));
+  GNN_TRY(hipMemsetAsync(w.cend, 0, kMaxSlices * 8, s));
+  hipLaunchKernelGGL(xcd_slice_bounds_kernel, dim3(blocks(I, kT)), dim3(kT), 0, s, w.it_slice2, I, w.cstart,
                      w.cend);
-  hipLaunchKernelGGL(xcd_rank_kernel, dim3(grid(I)), dim3(kT), 0, s, w.it_slice2, w.it_idx1, I,
+  hipLaunchKernelGGL(xcd_rank_kernel, dim3(blocks(I, kT)), dim3(kT), 0, s, w.it_slice2, w.it_idx1, I,
                      w.cstart, w.it_idx0);
   hipLaunchKernelGGL(xcd_bases_kernel, dim3(1), dim3(64), 0, s, w.cstart, w.cend, phases, w.hdr);
-  hipLaunchKernelGGL(xcd_pos_kernel, dim3(grid(I)), dim3(kT), 0, s, w.it_slice, w.it_idx0, I, w.hdr,
+  hipLaunchKernelGGL(xcd_pos_kernel, dim3(blocks(I, kT)), dim3(kT), 0, s, w.it_slice, w.it_idx0, I, w.hdr,
                      w.it_pos);
-  hipLaunchKernelGGL(xcd_first_item_kernel, dim3(grid(I)), dim3(kT), 0, s, w.it_row, I, w.first_item);
+  hipLaunchKernelGGL(xcd_first_item_kernel, dim3(blocks(I, kT)), dim3(kT), 0, s, w.it_row, I, w.first_item);
   tb = w.temp_bytes;
   const auto k_it = rocprim::make_transform_iterator(Count(0), KeptOp{w.moved_e, nnz});
-  PB_TRY(rocprim::exclusive_scan(w.temp, tb, k_it, w.kpre, int64_t(0), static_cast<size_t>(nnz + 1),
+  GNN_TRY(rocprim::exclusive_scan(w.temp, tb, k_it, w.kpre, int64_t(0), static_cast<size_t>(nnz + 1),
                                  rocprim::plus<int64_t>(), s));
   int64_t n_pos = 0;
-  if ((rc = sync_read(w.hdr + 4, &n_pos, 1, s)) != GNN_OK) return rc;
+  GNN_TRY(sync_read(w.hdr + 4, &n_pos, 1, s));
   counts[0] = I;
   counts[1] = n_pos;
   counts[2] = n_moved + 2 * (n_pos - I);  // item edges + two per pad position
@@ -830,18 +801,18 @@ extern "C" int gnn_xcd_hub_plan_fill(const void* workspace, const int64_t* rowpt
   const PosMap pm{w.hdr + 8, w.cstart, w.cend, w.it_idx1, phases};
   size_t tb = w.temp_bytes;
   const auto p_it = rocprim::make_transform_iterator(Count(0), PosCount{pm, w.it_cnt, n_pos});
-  PB_TRY(rocprim::exclusive_scan(w.temp, tb, p_it, items_rowptr, int64_t(0),
+  GNN_TRY(rocprim::exclusive_scan(w.temp, tb, p_it, items_rowptr, int64_t(0),
                                  static_cast<size_t>(n_pos + 1), rocprim::plus<int64_t>(), s));
-  hipLaunchKernelGGL(xcd_fill_items_kernel, dim3(grid(n_pos)), dim3(kT), 0, s, pm, w.hdr, n_pos,
+  hipLaunchKernelGGL(xcd_fill_items_kernel, dim3(blocks(n_pos, kT)), dim3(kT), 0, s, pm, w.hdr, n_pos,
                      items_rowptr,
                      w.it_e0, w.it_cnt, w.it_row, w.eid1, col_hub, val, items_col, items_val, pos_row);
   tb = w.temp_bytes;
   const auto r_it = rocprim::make_transform_iterator(Count(0), RestCount{rowptr, w.row_delta, n_rows});
-  PB_TRY(rocprim::exclusive_scan(w.temp, tb, r_it, rest_rowptr, int64_t(0),
+  GNN_TRY(rocprim::exclusive_scan(w.temp, tb, r_it, rest_rowptr, int64_t(0),
                                  static_cast<size_t>(n_rows + 1), rocprim::plus<int64_t>(), s));
-  hipLaunchKernelGGL(xcd_fill_kept_kernel, dim3(grid(nnz)), dim3(kT), 0, s, rowptr, w.row_e, nnz,
+  hipLaunchKernelGGL(xcd_fill_kept_kernel, dim3(blocks(nnz, kT)), dim3(kT), 0, s, rowptr, w.row_e, nnz,
                      w.moved_e, w.kpre, rest_rowptr, col_hub, val, rest_col, rest_val);
-  hipLaunchKernelGGL(xcd_fill_refs_kernel, dim3(grid(I)), dim3(kT), 0, s, rowptr, w.it_row, w.it_pos,
+  hipLaunchKernelGGL(xcd_fill_refs_kernel, dim3(blocks(I, kT)), dim3(kT), 0, s, rowptr, w.it_row, w.it_pos,
                      I, k, w.first_item, w.kpre, rest_rowptr, rest_col, rest_val);
   return launch_status();
 }

@@ -24,6 +24,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "common.hpp"
+#include "host.hpp"
 
 namespace gnn {
 
@@ -40,8 +41,6 @@ constexpr int64_t kRpBitmapBudget = 256ll << 20;  // bytes of bitmaps aimed at f
 constexpr uint32_t kRpEmpty = 0xffffffffu;
 constexpr int64_t kRpDimLimit = 0x7fffffffLL;  // n, k, m below 2^31 - 1
 
-static int64_t rp_align(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
-
 struct RpClass {  // rows of one class: lo < ub <= hi
   const int64_t* ub;
   int64_t lo, hi;
@@ -51,7 +50,7 @@ struct RpClass {  // rows of one class: lo < ub <= hi
 static int64_t rp_bitmap_words(int64_t m) { return (m + 63) / 64; }
 
 static int rp_heavy_grid(int64_t m) {
-  const int64_t bytes = rp_align(rp_bitmap_words(m) * 8, 256);
+  const int64_t bytes = up256(rp_bitmap_words(m) * 8);
   int64_t g = bytes > 0 ? kRpBitmapBudget / bytes : kRpHeavyGrid;
   if (g > kRpHeavyGrid) g = kRpHeavyGrid;
   if (g < kRpHeavyGridMin) g = kRpHeavyGridMin;
@@ -81,33 +80,24 @@ struct RpWs {
   unsigned long long* bitmap;  // [grid][words]
   int64_t words;      // per bitmap, padded to 256 B
   int grid;
-  int64_t total;
+  int64_t bytes;
 };
 
 static RpWs rp_carve(void* ws, int64_t n, int64_t m) {
+  Carve c{static_cast<char*>(ws)};
   RpWs w{};
-  char* p = static_cast<char*>(ws);
-  char* const p0 = p;
-  w.ub = reinterpret_cast<int64_t*>(p);
-  p += rp_align(n * 8, 256);
-  w.cnt = reinterpret_cast<int64_t*>(p);
-  p += rp_align((n + 1) * 8, 256);
-  w.mid_row = reinterpret_cast<int32_t*>(p);
-  p += rp_align(n * 4, 256);
-  w.heavy_row = reinterpret_cast<int32_t*>(p);
-  p += rp_align(n * 4, 256);
-  w.n_class = reinterpret_cast<int64_t*>(p);
-  p += 256;
-  w.err = reinterpret_cast<int32_t*>(p);
-  p += 256;
-  w.temp = p;
+  w.ub = c.take<int64_t>(n);
+  w.cnt = c.take<int64_t>(n + 1);
+  w.mid_row = c.take<int32_t>(n);
+  w.heavy_row = c.take<int32_t>(n);
+  w.n_class = c.take<int64_t>(2);
+  w.err = c.take<int32_t>(1);
   w.temp_bytes = rp_temp_bytes(n);
-  p += rp_align(static_cast<int64_t>(w.temp_bytes), 256);
-  w.bitmap = reinterpret_cast<unsigned long long*>(p);
-  w.words = rp_align(rp_bitmap_words(m) * 8, 256) / 8;
+  w.temp = c.take<char>(static_cast<int64_t>(w.temp_bytes));
+  w.words = up256(rp_bitmap_words(m) * 8) / 8;
   w.grid = rp_heavy_grid(m);
-  p += w.words * 8 * w.grid;
-  w.total = p - p0;
+  w.bitmap = c.take<unsigned long long>(w.words * w.grid);
+  w.bytes = c.used;
   return w;
 }
 
@@ -439,10 +429,6 @@ __global__ __launch_bounds__(kRpBlock) void rp_heavy_kernel(
   }
 }
 
-static inline unsigned rp_grid(int64_t n, int per) {
-  return static_cast<unsigned>((n + per - 1) / per);
-}
-
 static int rp_check_dims(int64_t n, int64_t k, int64_t m, int64_t nnz_a, int64_t nnz_b) {
   if (n < 0 || k < 0 || m < 0 || nnz_a < 0 || nnz_b < 0) return GNN_E_ARG;
   if (n >= kRpDimLimit || k >= kRpDimLimit || m >= kRpDimLimit) return GNN_E_UNSUPPORTED;
@@ -454,7 +440,7 @@ static void rp_launch_rows(const int64_t* arp, const int32_t* acol, const int64_
                            const int32_t* bcol, int64_t n, const RpWs& w, const int64_t* crp,
                            int32_t* ccol, int64_t nnz_c, hipStream_t s) {
   if (n == 0) return;
-  hipLaunchKernelGGL(rp_short_kernel<FILL>, dim3(rp_grid(n, kRpWaves)), dim3(kRpBlock), 0, s, arp,
+  hipLaunchKernelGGL(rp_short_kernel<FILL>, dim3(blocks(n, kRpWaves)), dim3(kRpBlock), 0, s, arp,
                      acol, brp, bcol, n, w.ub, w.cnt, crp, ccol, nnz_c);
   const int64_t mid_grid = n < kRpMidGrid ? n : kRpMidGrid;
   hipLaunchKernelGGL(rp_mid_kernel<FILL>, dim3(static_cast<unsigned>(mid_grid)), dim3(kRpBlock), 0,
@@ -474,7 +460,7 @@ extern "C" int64_t gnn_relation_product_workspace_bytes(int64_t n, int64_t k, in
   const int rc = rp_check_dims(n, k, m, nnz_a, nnz_b);
   if (rc != GNN_OK) return rc;
   // the terms: O(n) row arrays and rocPRIM's temporaries, and a fixed number of m-bit bitmaps
-  return rp_carve(nullptr, n, m).total + 256;
+  return rp_carve(nullptr, n, m).bytes + 256;
 }
 
 extern "C" int gnn_relation_product_class_limits(int64_t* short_max, int64_t* mid_max) {
@@ -495,46 +481,38 @@ extern "C" int gnn_relation_product_count(const int64_t* a_rowptr, const int32_t
   if (!a_rowptr || !b_rowptr || !c_rowptr || !nnz_out || !workspace || (nnz_a > 0 && !a_col) ||
       (nnz_b > 0 && !b_col))
     return GNN_E_ARG;
-  if (workspace_bytes < gnn_relation_product_workspace_bytes(n, k, m, nnz_a, nnz_b))
-    return GNN_E_ARG;
-  hipStream_t s = static_cast<hipStream_t>(stream);
   RpWs w = rp_carve(workspace, n, m);
-  hipError_t e = hipMemsetAsync(w.err, 0, sizeof(int32_t), s);
-  if (e == hipSuccess) e = hipMemsetAsync(w.n_class, 0, 2 * sizeof(int64_t), s);
-  if (e == hipSuccess) e = hipMemsetAsync(w.bitmap, 0, static_cast<size_t>(w.words) * 8 * w.grid, s);
-  if (e != hipSuccess) return static_cast<int>(e);
+  if (workspace_bytes < w.bytes + 256) return GNN_E_ARG;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  GNN_TRY(hipMemsetAsync(w.err, 0, sizeof(int32_t), s));
+  GNN_TRY(hipMemsetAsync(w.n_class, 0, 2 * sizeof(int64_t), s));
+  GNN_TRY(hipMemsetAsync(w.bitmap, 0, static_cast<size_t>(w.words) * 8 * w.grid, s));
   const int64_t va = (n > nnz_a ? n : nnz_a) + 1, vb = (k > nnz_b ? k : nnz_b) + 1;
-  hipLaunchKernelGGL(rp_validate_kernel, dim3(rp_grid(va, 256)), dim3(256), 0, s, a_rowptr, a_col,
+  hipLaunchKernelGGL(rp_validate_kernel, dim3(blocks(va, 256)), dim3(256), 0, s, a_rowptr, a_col,
                      n, k, nnz_a, w.err);
-  hipLaunchKernelGGL(rp_validate_kernel, dim3(rp_grid(vb, 256)), dim3(256), 0, s, b_rowptr, b_col,
+  hipLaunchKernelGGL(rp_validate_kernel, dim3(blocks(vb, 256)), dim3(256), 0, s, b_rowptr, b_col,
                      k, m, nnz_b, w.err);
   int32_t herr = 0;
-  e = hipMemcpyAsync(&herr, w.err, sizeof(int32_t), hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) return static_cast<int>(e);
+  GNN_TRY(sync_read(w.err, &herr, 1, s));
   if (herr) return GNN_E_ARG;  // an id outside its range (or a broken rowptr): nothing follows it
-  hipLaunchKernelGGL(rp_bound_kernel, dim3(rp_grid(n + 1, 256)), dim3(256), 0, s, a_rowptr, a_col,
+  hipLaunchKernelGGL(rp_bound_kernel, dim3(blocks(n + 1, 256)), dim3(256), 0, s, a_rowptr, a_col,
                      b_rowptr, n, w.ub, w.cnt);
   if (n > 0) {
     size_t tb = w.temp_bytes;
-    e = rocprim::select(w.temp, tb, rocprim::counting_iterator<int32_t>(0), w.mid_row, w.n_class,
-                        static_cast<size_t>(n), RpClass{w.ub, kRpShortMax, kRpMidMax}, s);
-    if (e != hipSuccess) return static_cast<int>(e);
+    GNN_TRY(rocprim::select(w.temp, tb, rocprim::counting_iterator<int32_t>(0), w.mid_row,
+                            w.n_class, static_cast<size_t>(n),
+                            RpClass{w.ub, kRpShortMax, kRpMidMax}, s));
     tb = w.temp_bytes;
-    e = rocprim::select(w.temp, tb, rocprim::counting_iterator<int32_t>(0), w.heavy_row,
-                        w.n_class + 1, static_cast<size_t>(n),
-                        RpClass{w.ub, kRpMidMax, INT64_MAX}, s);
-    if (e != hipSuccess) return static_cast<int>(e);
+    GNN_TRY(rocprim::select(w.temp, tb, rocprim::counting_iterator<int32_t>(0), w.heavy_row,
+                            w.n_class + 1, static_cast<size_t>(n),
+                            RpClass{w.ub, kRpMidMax, INT64_MAX}, s));
   }
   rp_launch_rows<false>(a_rowptr, a_col, b_rowptr, b_col, n, w, nullptr, nullptr, 0, s);
   size_t tb = w.temp_bytes;
-  e = rocprim::exclusive_scan(w.temp, tb, w.cnt, c_rowptr, static_cast<int64_t>(0),
-                              static_cast<size_t>(n + 1), rocprim::plus<int64_t>(), s);
-  if (e != hipSuccess) return static_cast<int>(e);
+  GNN_TRY(rocprim::exclusive_scan(w.temp, tb, w.cnt, c_rowptr, static_cast<int64_t>(0),
+                                  static_cast<size_t>(n + 1), rocprim::plus<int64_t>(), s));
   int64_t nnz = 0;
-  e = hipMemcpyAsync(&nnz, c_rowptr + n, sizeof(int64_t), hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) return static_cast<int>(e);
+  GNN_TRY(sync_read(c_rowptr + n, &nnz, 1, s));
   *nnz_out = nnz;
   return launch_status();
 }
@@ -550,10 +528,9 @@ extern "C" int gnn_relation_product_fill(const int64_t* a_rowptr, const int32_t*
   if (!a_rowptr || !b_rowptr || !c_rowptr || !workspace || nnz_c < 0 || (nnz_c > 0 && !c_col) ||
       (nnz_a > 0 && !a_col) || (nnz_b > 0 && !b_col))
     return GNN_E_ARG;
-  if (workspace_bytes < gnn_relation_product_workspace_bytes(n, k, m, nnz_a, nnz_b))
-    return GNN_E_ARG;
-  if (nnz_c == 0) return GNN_OK;
   RpWs w = rp_carve(workspace, n, m);
+  if (workspace_bytes < w.bytes + 256) return GNN_E_ARG;
+  if (nnz_c == 0) return GNN_OK;
   rp_launch_rows<true>(a_rowptr, a_col, b_rowptr, b_col, n, w, c_rowptr, c_col, nnz_c,
                        static_cast<hipStream_t>(stream));
   return launch_status();

@@ -34,6 +34,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "common.hpp"
+#include "host.hpp"
 
 namespace gnn {
 
@@ -48,8 +49,6 @@ constexpr int kSbWaves = kSbBlock / kWave;
 constexpr int kSbChunk = GNN_SB_CHUNK;
 constexpr int kSbU = GNN_SB_U;
 constexpr int kSbGrid = 2048;  // the chunk / combine passes: a fixed grid, sizes read on the device
-
-static int64_t sb_align(int64_t v) { return (v + 255) / 256 * 256; }
 
 // M (k + 1), or -1 where it does not fit an int32 slot id
 static int64_t sb_slots(int64_t M, int64_t k) {
@@ -339,8 +338,7 @@ template <int LPR, typename A>
 static int launch_sage_scatter(const A& a, hipStream_t s) {
   const int64_t blocks = (a.n_prev * LPR + kSbBlock - 1) / kSbBlock;
   if (blocks > 0x7fffffffLL) return GNN_E_UNSUPPORTED;
-  hipError_t e = hipMemsetAsync(a.count, 0, 2 * sizeof(int32_t), s);
-  if (e != hipSuccess) return static_cast<int>(e);
+  GNN_TRY(hipMemsetAsync(a.count, 0, 2 * sizeof(int32_t), s));
   hipLaunchKernelGGL((sage_scatter_rows_kernel<LPR, A>), dim3(static_cast<unsigned>(blocks)),
                      dim3(kSbBlock), 0, s, a);
   int64_t g = (static_cast<int64_t>(a.max_tasks) + kSbWaves - 1) / kSbWaves;
@@ -355,54 +353,77 @@ static int launch_sage_scatter(const A& a, hipStream_t s) {
 }
 
 // the workspace of the scatter: counters | split targets | chunks | partial rows
-struct SbLayout {
-  int64_t max_long, max_tasks, off_longs, off_tasks, off_part, bytes;
+struct SbWs {
+  int32_t* count;  // SbArgs' pieces
+  int2* longs;
+  int2* tasks;
+  float* part;
+  int32_t max_long, max_tasks;  // n_slots fits an int32
+  int64_t bytes;
 };
-static SbLayout sb_layout(int64_t n_slots, int64_t F) {
-  SbLayout l;
-  l.max_long = n_slots / kSbChunk + 1;       // every split list holds more than kSbChunk slots
-  l.max_tasks = 2 * (n_slots / kSbChunk) + 2;  // sum of ceil(len / chunk) <= n / chunk + lists
-  l.off_longs = 256;
-  l.off_tasks = l.off_longs + sb_align(l.max_long * 8);
-  l.off_part = l.off_tasks + sb_align(l.max_tasks * 8);
-  l.bytes = l.off_part + sb_align(l.max_tasks * F * 4);
-  return l;
+static SbWs sb_carve(void* ws, int64_t n_slots, int64_t F) {
+  Carve c{static_cast<char*>(ws)};
+  SbWs w{};
+  // every split list holds more than kSbChunk slots; sum of ceil(len / chunk) <= n / chunk + lists
+  w.max_long = static_cast<int32_t>(n_slots / kSbChunk + 1);
+  w.max_tasks = static_cast<int32_t>(2 * (n_slots / kSbChunk) + 2);
+  w.count = c.take<int32_t>(2);
+  w.longs = c.take<int2>(w.max_long);
+  w.tasks = c.take<int2>(w.max_tasks);
+  w.part = c.take<float>(w.max_tasks * F);
+  w.bytes = c.used;
+  return w;
+}
+
+// the workspace of a transpose over n slots: keys | sorted keys | rocPRIM's temporary, sized
+// for 32-bit keys
+struct SbTransposeWs {
+  uint32_t* k0;
+  uint32_t* k1;
+  void* temp;
+  size_t temp_bytes;
+  int64_t bytes;
+};
+static SbTransposeWs sb_transpose_carve(void* ws, int64_t n) {
+  Carve c{static_cast<char*>(ws)};
+  SbTransposeWs w{};
+  w.k0 = c.take<uint32_t>(n);
+  w.k1 = c.take<uint32_t>(n);
+  w.temp_bytes = sb_sort_temp(n > 0 ? n : 1, 32);
+  w.temp = c.raw(static_cast<int64_t>(w.temp_bytes));
+  c.raw(1 << 20);
+  w.bytes = c.used;
+  return w;
 }
 
 }  // namespace gnn
 
 using namespace gnn;
 
-// the workspace of a transpose over n slots: keys | sorted keys | rocPRIM's temporary
-static int64_t sb_transpose_bytes(int64_t n) {
-  return 2 * sb_align(n * 4) + static_cast<int64_t>(sb_sort_temp(n > 0 ? n : 1, 32)) + (1 << 20);
-}
-
 // the body of both transposes: the arguments are checked, n = the number of slots
 template <bool CENTRE>
 static int sb_transpose(const int64_t* cidx, const int64_t* idx, int64_t ldi, int64_t M, int64_t k,
                         int64_t n_prev, int64_t n, int64_t* ptr, int32_t* slot, int32_t* err_flag,
                         void* workspace, int64_t workspace_bytes, void* stream) {
+  const SbTransposeWs w = sb_transpose_carve(workspace, n);
+  if (workspace_bytes < w.bytes) return GNN_E_ARG;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  char* w = static_cast<char*>(workspace);
-  uint32_t* k0 = reinterpret_cast<uint32_t*>(w);
-  uint32_t* k1 = reinterpret_cast<uint32_t*>(w + sb_align(n * 4));
-  void* temp = w + 2 * sb_align(n * 4);
   if (n > 0) {
+    // the temporary of this call's key width must fit what follows the keys
     const unsigned bits = sb_key_bits(n_prev);
     size_t tb = sb_sort_temp(n, bits);
-    if (static_cast<int64_t>(tb) > workspace_bytes - 2 * sb_align(n * 4)) return GNN_E_ARG;
+    const int64_t room = workspace_bytes - (static_cast<char*>(w.temp) - static_cast<char*>(workspace));
+    if (static_cast<int64_t>(tb) > room) return GNN_E_ARG;
     int64_t g = (n + kSbBlock - 1) / kSbBlock;
     g = g < 4 * kSbGrid ? g : 4 * kSbGrid;
     hipLaunchKernelGGL(sage_slot_keys_kernel<CENTRE>, dim3(static_cast<unsigned>(g)),
-                       dim3(kSbBlock), 0, s, cidx, idx, ldi, M, k, n_prev, k0, err_flag);
-    hipError_t e = rocprim::radix_sort_pairs(temp, tb, k0, k1, rocprim::counting_iterator<int32_t>(0),
-                                             slot, static_cast<size_t>(n), 0, bits, s);
-    if (e != hipSuccess) return static_cast<int>(e);
+                       dim3(kSbBlock), 0, s, cidx, idx, ldi, M, k, n_prev, w.k0, err_flag);
+    GNN_TRY(rocprim::radix_sort_pairs(w.temp, tb, w.k0, w.k1, rocprim::counting_iterator<int32_t>(0),
+                                      slot, static_cast<size_t>(n), 0, bits, s));
   }
   const int64_t pb = (n_prev + 1 + kSbBlock - 1) / kSbBlock;
-  hipLaunchKernelGGL(sage_slot_ptr_kernel, dim3(static_cast<unsigned>(pb)), dim3(kSbBlock), 0, s, k1,
-                     n, n_prev, ptr);
+  hipLaunchKernelGGL(sage_slot_ptr_kernel, dim3(static_cast<unsigned>(pb)), dim3(kSbBlock), 0, s,
+                     w.k1, n, n_prev, ptr);
   return launch_status();
 }
 
@@ -410,7 +431,7 @@ extern "C" int64_t gnn_sage_maps_transpose_workspace_bytes(int64_t M, int64_t k)
   if (M < 0 || k < 0) return GNN_E_ARG;
   const int64_t n = sb_slots(M, k);
   if (n < 0) return GNN_E_UNSUPPORTED;
-  return sb_transpose_bytes(n);
+  return sb_transpose_carve(nullptr, n).bytes;
 }
 
 extern "C" int gnn_sage_maps_transpose(const int64_t* cidx, const int64_t* idx, int64_t ldi,
@@ -421,7 +442,6 @@ extern "C" int gnn_sage_maps_transpose(const int64_t* cidx, const int64_t* idx, 
   if (M > 0 && (!cidx || !slot || (k > 0 && (!idx || ldi < k)))) return GNN_E_ARG;
   const int64_t n = sb_slots(M, k);
   if (n < 0 || n_prev >= 0x7fffffffLL) return GNN_E_UNSUPPORTED;
-  if (workspace_bytes < gnn_sage_maps_transpose_workspace_bytes(M, k)) return GNN_E_ARG;
   return sb_transpose<true>(cidx, idx, ldi, M, k, n_prev, n, ptr, slot, err_flag, workspace,
                             workspace_bytes, stream);
 }
@@ -431,7 +451,7 @@ extern "C" int64_t gnn_sage_maps_transpose_nbr_workspace_bytes(int64_t M, int64_
   if (M < 0 || k < 0) return GNN_E_ARG;
   const int64_t n = sb_slots_nbr(M, k);
   if (n < 0) return GNN_E_UNSUPPORTED;
-  return sb_transpose_bytes(n);
+  return sb_transpose_carve(nullptr, n).bytes;
 }
 
 extern "C" int gnn_sage_maps_transpose_nbr(const int64_t* idx, int64_t ldi, int64_t M, int64_t k,
@@ -442,7 +462,6 @@ extern "C" int gnn_sage_maps_transpose_nbr(const int64_t* idx, int64_t ldi, int6
   if (M > 0 && k > 0 && (!idx || !slot || ldi < k)) return GNN_E_ARG;
   const int64_t n = sb_slots_nbr(M, k);
   if (n < 0 || n_prev >= 0x7fffffffLL) return GNN_E_UNSUPPORTED;
-  if (workspace_bytes < gnn_sage_maps_transpose_nbr_workspace_bytes(M, k)) return GNN_E_ARG;
   return sb_transpose<false>(nullptr, idx, ldi, M, k, n_prev, n, ptr, slot, err_flag, workspace,
                              workspace_bytes, stream);
 }
@@ -456,7 +475,7 @@ extern "C" int64_t gnn_sage_scatter_concat_workspace_bytes(int64_t M, int64_t k,
   if (M < 0 || k < 0 || feat < 0) return GNN_E_ARG;
   const int64_t n = sb_slots(M, k);
   if (n < 0 || !gnn_sage_scatter_concat_supported(feat)) return GNN_E_UNSUPPORTED;
-  return sb_layout(n, feat).bytes;
+  return sb_carve(nullptr, n, feat).bytes;
 }
 
 template <typename A>
@@ -494,17 +513,14 @@ extern "C" int gnn_sage_scatter_concat_maxpool_f32(const float* dbuf, int64_t ld
       k > 255)
     return GNN_E_UNSUPPORTED;
   if (ldd < 2 * feat || ldx < feat || lda < feat) return GNN_E_ARG;
-  const SbLayout l = sb_layout(n, feat);
-  if (workspace_bytes < l.bytes) return GNN_E_ARG;
+  const SbWs w = sb_carve(workspace, n, feat);
+  if (workspace_bytes < w.bytes) return GNN_E_ARG;
   if (ldd % 4 || ldx % 4 || lda % 4 || !aligned_to(dbuf, 16) || !aligned_to(dx, 16) ||
       !aligned_to(arg, 4) || !aligned_to(workspace, 16))
     return GNN_E_ALIGN;
   if (n_prev == 0) return GNN_OK;
-  char* w = static_cast<char*>(workspace);
-  SbMaskArgs a{{dbuf, ldd, ptr, slot, M, k, n_prev, n, 1.f, dx, ldx, reinterpret_cast<int32_t*>(w),
-                reinterpret_cast<int2*>(w + l.off_longs), reinterpret_cast<int2*>(w + l.off_tasks),
-                reinterpret_cast<float*>(w + l.off_part), static_cast<int32_t>(l.max_long),
-                static_cast<int32_t>(l.max_tasks)},
+  SbMaskArgs a{{dbuf, ldd, ptr, slot, M, k, n_prev, n, 1.f, dx, ldx, w.count, w.longs, w.tasks,
+                w.part, w.max_long, w.max_tasks},
                arg, lda};
   return dispatch_sage_scatter(a, feat, static_cast<hipStream_t>(stream));
 }
@@ -519,17 +535,14 @@ extern "C" int gnn_sage_scatter_concat_f32(const float* dbuf, int64_t ldd, const
   if (n < 0 || n_prev >= 0x7fffffffLL || !gnn_sage_scatter_concat_supported(feat))
     return GNN_E_UNSUPPORTED;
   if (ldd < 2 * feat || ldx < feat) return GNN_E_ARG;
-  const SbLayout l = sb_layout(n, feat);
-  if (workspace_bytes < l.bytes) return GNN_E_ARG;
+  const SbWs w = sb_carve(workspace, n, feat);
+  if (workspace_bytes < w.bytes) return GNN_E_ARG;
   if (ldd % 4 || ldx % 4 || !aligned_to(dbuf, 16) || !aligned_to(dx, 16) ||
       !aligned_to(workspace, 16))
     return GNN_E_ALIGN;
   if (n_prev == 0) return GNN_OK;
-  char* w = static_cast<char*>(workspace);
   SbArgs a{dbuf, ldd, ptr, slot, M, k, n_prev, n, k > 0 ? 1.0f / static_cast<float>(k) : 0.f, dx,
-           ldx, reinterpret_cast<int32_t*>(w), reinterpret_cast<int2*>(w + l.off_longs),
-           reinterpret_cast<int2*>(w + l.off_tasks), reinterpret_cast<float*>(w + l.off_part),
-           static_cast<int32_t>(l.max_long), static_cast<int32_t>(l.max_tasks)};
+           ldx, w.count, w.longs, w.tasks, w.part, w.max_long, w.max_tasks};
   return dispatch_sage_scatter(a, feat, static_cast<hipStream_t>(stream));
 }
 
@@ -538,7 +551,7 @@ extern "C" int64_t gnn_sage_scatter_agg_workspace_bytes(int64_t M, int64_t k, in
   if (M < 0 || k < 0 || feat < 0) return GNN_E_ARG;
   const int64_t n = sb_slots_nbr(M, k);
   if (n < 0 || !gnn_sage_scatter_concat_supported(feat)) return GNN_E_UNSUPPORTED;
-  return sb_layout(n, feat).bytes;
+  return sb_carve(nullptr, n, feat).bytes;
 }
 
 extern "C" int64_t gnn_sage_scatter_agg_maxpool_workspace_bytes(int64_t M, int64_t k,
@@ -558,17 +571,14 @@ extern "C" int gnn_sage_scatter_agg_f32(const float* dbuf, int64_t ldd, const in
   if (n < 0 || n_prev >= 0x7fffffffLL || !gnn_sage_scatter_concat_supported(feat))
     return GNN_E_UNSUPPORTED;
   if (ldd < feat || ldx < feat) return GNN_E_ARG;
-  const SbLayout l = sb_layout(n, feat);
-  if (workspace_bytes < l.bytes) return GNN_E_ARG;
+  const SbWs w = sb_carve(workspace, n, feat);
+  if (workspace_bytes < w.bytes) return GNN_E_ARG;
   if (ldd % 4 || ldx % 4 || !aligned_to(dbuf, 16) || !aligned_to(dx, 16) ||
       !aligned_to(workspace, 16))
     return GNN_E_ALIGN;
   if (n_prev == 0) return GNN_OK;
-  char* w = static_cast<char*>(workspace);
   SbAggArgs a{{dbuf, ldd, ptr, slot, M, k, n_prev, n, k > 0 ? 1.0f / static_cast<float>(k) : 0.f,
-               dx, ldx, reinterpret_cast<int32_t*>(w), reinterpret_cast<int2*>(w + l.off_longs),
-               reinterpret_cast<int2*>(w + l.off_tasks), reinterpret_cast<float*>(w + l.off_part),
-               static_cast<int32_t>(l.max_long), static_cast<int32_t>(l.max_tasks)}};
+               dx, ldx, w.count, w.longs, w.tasks, w.part, w.max_long, w.max_tasks}};
   return dispatch_sage_scatter(a, feat, static_cast<hipStream_t>(stream));
 }
 
@@ -586,18 +596,14 @@ extern "C" int gnn_sage_scatter_agg_maxpool_f32(const float* dbuf, int64_t ldd, 
       k > 255)
     return GNN_E_UNSUPPORTED;
   if (ldd < feat || ldx < feat || lda < feat) return GNN_E_ARG;
-  const SbLayout l = sb_layout(n, feat);
-  if (workspace_bytes < l.bytes) return GNN_E_ARG;
+  const SbWs w = sb_carve(workspace, n, feat);
+  if (workspace_bytes < w.bytes) return GNN_E_ARG;
   if (ldd % 4 || ldx % 4 || lda % 4 || !aligned_to(dbuf, 16) || !aligned_to(dx, 16) ||
       !aligned_to(arg, 4) || !aligned_to(workspace, 16))
     return GNN_E_ALIGN;
   if (n_prev == 0) return GNN_OK;
-  char* w = static_cast<char*>(workspace);
   SbAggMaskArgs a{{{dbuf, ldd, ptr, slot, M, k, n_prev, n, 1.f, dx, ldx,
-                    reinterpret_cast<int32_t*>(w), reinterpret_cast<int2*>(w + l.off_longs),
-                    reinterpret_cast<int2*>(w + l.off_tasks),
-                    reinterpret_cast<float*>(w + l.off_part), static_cast<int32_t>(l.max_long),
-                    static_cast<int32_t>(l.max_tasks)},
+                    w.count, w.longs, w.tasks, w.part, w.max_long, w.max_tasks},
                    arg, lda}};
   return dispatch_sage_scatter(a, feat, static_cast<hipStream_t>(stream));
 }
