@@ -10,8 +10,20 @@ state_dict keys as the reference):
 * ``graphneuralnetwork_amd.graphsage`` -- SageLayer, GraphSAGE, Aggregator (GraphSAGE/*.py)
 * ``graphneuralnetwork_amd.loss``      -- supervised_loss, accuracy: the loss / accuracy /
                                           backward lines of the train_eval.py loops
+* ``graphneuralnetwork_amd.gtn``       -- GTConv, GTLayer, GTN_Model, norm  (GTN/models/*.py);
+                                          also importable from the package itself
 
 The aggregation hot paths run as hand-written gfx950 HIP kernels in
 ``lib/libgnn_mi355x.so`` behind the C-ABI of ``include/gnn_mi355x.h``.
 """
 __version__ = "0.1.0"
+
+_GTN = ("GTConv", "GTLayer", "GTN_Model")
+
+
+def __getattr__(name):
+    # resolved on first use: importing the package stays free of torch
+    if name in _GTN:
+        from . import gtn
+        return getattr(gtn, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -19,6 +19,11 @@ metapath (``collect_f.__call__``, HAN/utils/data_utils.py:92-101). Here the slic
 subgraph of a ``CsrGraph`` written as a ``CsrGraph`` [b, b] (csrc/induced_subgraph.hip:
 ``gnn_induced_subgraph_map`` / ``_count`` / ``_fill``; ``induced_subgraphs``), rows ascending by
 position, values carried, and ``collect_f`` is the reference's class over it.
+
+The reference's GTN takes its T edge types as one dense ``[N, N, T]`` tensor (GTN/run.py). Here
+``edge_type_graph`` turns the relations into an ``EdgeTypeGraph``: the union pattern U, each
+relation's values over it, and the cached product patterns S_{l+1} = (S_l . U) > 0 that
+``gtn.GTN_Model`` computes values on (csrc/gtn.hip).
 """
 from __future__ import annotations
 
@@ -393,3 +398,156 @@ class collect_f:
         else:
             adj = [a[idx.to(a.device)][:, idx.to(a.device)] for a in self.HGs_adj]
         return adj, self.features[idx], self.labels[idx]
+
+
+# ------------------------------------------------- edge-type graphs: the GTN input on CSR patterns
+class Pattern:
+    """A CSR pattern (rows ascending, no duplicates; a CsrGraph whose values are not read) with
+    its cached column view: ``T`` is the pattern of the transpose, and values [C, nnz] over this
+    pattern become values over ``T`` as ``v[:, perm]`` (``T.perm`` is the inverse, so every
+    move between the two layouts is a gather)."""
+
+    def __init__(self, g: CsrGraph):
+        self.g = g
+        self._t: "Pattern | None" = None
+        self._perm = None
+        self.next: "Pattern | None" = None       # (this . U) > 0, set by EdgeTypeGraph
+        self.checked: set = set()                # operand sets the product kernel has validated
+
+    @property
+    def nnz(self) -> int:
+        return self.g.nnz
+
+    @property
+    def T(self) -> "Pattern":
+        if self._t is None:
+            _, _, eid, gt = self.g.transpose_eid()
+            t = Pattern(gt)
+            inv = torch.empty_like(eid)
+            inv[eid] = torch.arange(eid.numel(), device=eid.device, dtype=eid.dtype)
+            self._perm, t._perm = eid, inv
+            self._t, t._t = t, self
+        return self._t
+
+    @property
+    def perm(self) -> torch.Tensor:
+        self.T
+        return self._perm
+
+
+class EdgeTypeGraph:
+    """The T relations of a heterogeneous graph over one node set, as the sparse GTN reads
+    them: ``U`` the union pattern (CsrGraph [n, n], columns ascending, no duplicates) and
+    ``tval`` [T, nnz_U] each relation's value at each union entry (0 where it has none). The
+    product patterns S_1 = U, S_{l+1} = (S_l . U) > 0 are built once (``relation_product``) and
+    cached here with their column views."""
+
+    def __init__(self, U: CsrGraph, tval: torch.Tensor):
+        self.U, self.tval = U, tval
+        self.n, self.T = U.n_rows, int(tval.shape[0])
+        self._pattern = Pattern(U)
+        self._tval_t = None
+
+    @property
+    def device(self) -> torch.device:
+        return self.U.device
+
+    @property
+    def pattern(self) -> Pattern:
+        return self._pattern
+
+    @property
+    def tval_t(self) -> torch.Tensor:
+        """``tval`` over the column view of U (the values of the transposed relations)."""
+        if self._tval_t is None:
+            self._tval_t = self.tval[:, self._pattern.perm].contiguous()
+        return self._tval_t
+
+    def product_pattern(self, p: Pattern) -> Pattern:
+        """(p . U) > 0 as a Pattern, built once per p."""
+        if p.next is None:
+            p.next = Pattern(relation_product(p.g, self.U))
+        return p.next
+
+    def S(self, l: int) -> Pattern:
+        """S_1 = U and S_{l+1} = (S_l . U) > 0."""
+        p = self._pattern
+        for _ in range(l - 1):
+            p = self.product_pattern(p)
+        return p
+
+    def to(self, device) -> "EdgeTypeGraph":
+        return EdgeTypeGraph(self.U.to(device), self.tval.to(device))
+
+
+def _relation_coo(rel):
+    """(row, col, val, n_rows, n_cols) of one relation, every stored entry kept."""
+    if isinstance(rel, CsrGraph):
+        row = torch.repeat_interleave(
+            torch.arange(rel.n_rows, device=rel.device, dtype=torch.int64),
+            rel.rowptr[1:] - rel.rowptr[:-1])
+        return row, rel.col.to(torch.int64), rel.val, rel.n_rows, rel.n_cols
+    if isinstance(rel, torch.Tensor):
+        if rel.dim() != 2:
+            raise TypeError("a relation is a 2-D matrix")
+        if rel.layout == torch.strided:
+            idx = (rel != 0).nonzero()
+            return idx[:, 0], idx[:, 1], rel[rel != 0], rel.shape[0], rel.shape[1]
+        coo = rel.to_sparse_coo() if rel.layout != torch.sparse_coo else rel
+        return coo._indices()[0], coo._indices()[1], coo._values(), rel.shape[0], rel.shape[1]
+    if hasattr(rel, "tocoo"):  # a scipy sparse matrix: never imported here, only recognised
+        coo = rel.tocoo()
+        return (torch.from_numpy(coo.row.astype("int64")), torch.from_numpy(coo.col.astype("int64")),
+                torch.from_numpy(coo.data.astype("float64")), int(coo.shape[0]), int(coo.shape[1]))
+    raise TypeError("a relation is a scipy sparse matrix, a torch tensor or a CsrGraph")
+
+
+def edge_type_graph(relations, device=None) -> EdgeTypeGraph:
+    """The ``EdgeTypeGraph`` of T square relations over one node set: a list of ``CsrGraph``s,
+    torch sparse or dense 2-D tensors or scipy sparse matrices (recognised, never imported), or
+    the reference's dense ``[N, N, T]`` tensor (GTN/run.py builds it from the edge lists).
+    Duplicates within one relation are summed, as scipy's constructor does; entries equal to 0
+    are not edges; a negative value raises ``ValueError`` (the reference's ``deg_inv == inf``
+    test only catches a degree of +0). ``device``: where the graph lives (default: the
+    relations' own)."""
+    if isinstance(relations, torch.Tensor) or hasattr(relations, "ndim") and \
+            not hasattr(relations, "tocoo"):
+        stack = torch.as_tensor(relations)
+        if stack.dim() != 3 or stack.shape[0] != stack.shape[1]:
+            raise ValueError(f"a dense edge-type tensor is [N, N, T] (got {tuple(stack.shape)})")
+        relations = [stack[:, :, t] for t in range(stack.shape[2])]
+    relations = list(relations)
+    if not relations:
+        raise ValueError("an edge-type graph needs at least one relation")
+    keys, vals, n = [], [], None
+    for rel in relations:
+        row, col, val, nr, nc = _relation_coo(rel)
+        if nr != nc or (n is not None and nr != n):
+            raise ValueError("the relations are square and share one node set")
+        n = nr
+        if device is not None:
+            row, col, val = row.to(device), col.to(device), val.to(device)
+        if val.numel() and bool((val < 0).any()):
+            raise ValueError("a relation with negative entries has no GTN normalisation here: "
+                             "the reference's deg_inv == inf test only catches a degree of +0")
+        if row.numel() and (int(row.min()) < 0 or int(row.max()) >= n or int(col.min()) < 0
+                            or int(col.max()) >= n):
+            raise IndexError("relation index out of range")
+        key, inverse = torch.unique(row.to(torch.int64) * n + col.to(torch.int64),
+                                    return_inverse=True)
+        total = torch.zeros(key.numel(), dtype=torch.float64, device=key.device)
+        total.index_add_(0, inverse, val.to(torch.float64))     # duplicates summed
+        keep = total != 0
+        keys.append(key[keep])
+        vals.append(total[keep])
+    dev = keys[0].device
+    union = torch.unique(torch.cat(keys))
+    tval = torch.zeros((len(relations), union.numel()), dtype=torch.float32, device=dev)
+    for t, (key, val) in enumerate(zip(keys, vals)):
+        tval[t, torch.searchsorted(union, key)] = val.to(torch.float32)
+    rowptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    if union.numel():
+        torch.cumsum(torch.bincount(union // n, minlength=n), 0, out=rowptr[1:])
+    U = CsrGraph(rowptr, (union % n).to(torch.int32).contiguous(),
+                 torch.ones(union.numel(), dtype=torch.float32, device=dev), n, n)
+    return EdgeTypeGraph(U, tval)

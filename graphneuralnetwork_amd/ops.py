@@ -2797,3 +2797,244 @@ def gat_backward(g: CsrGraph, wh: torch.Tensor, el: torch.Tensor, er: torch.Tens
         part=part.data_ptr(), stream=stream)
     mark(None)
     return dwh, dout, dl, der
+
+
+# ------------------------------------------------- GTN: values over fixed CSR patterns (gtn.hip)
+# A pattern is a CsrGraph whose values are not read; values travel beside it as [C, nnz]
+# channel-major float32. The C entries take 1 <= C <= 8: more channels are looped here.
+GTN_MAX_CHANNELS = 8
+
+
+def masked_product_class_limits() -> tuple[int, int]:
+    """(lane_max, wave_chunk) of gnn_masked_product_f32: the longest walked row summed by the P
+    entry's own lane, and how many walked entries a wavefront takes at a time above it."""
+    import ctypes
+    a, b = ctypes.c_int64(0), ctypes.c_int64(0)
+    _lib.check(_lib.load().gnn_masked_product_class_limits(ctypes.byref(a), ctypes.byref(b)),
+               "gnn_masked_product_class_limits")
+    return int(a.value), int(b.value)
+
+
+def _entry_rows(g: CsrGraph) -> torch.Tensor:
+    """The row id of every stored entry (int64 [nnz], cached on the graph)."""
+    r = g._plans.get("_entry_rows")
+    if r is None:
+        r = torch.repeat_interleave(
+            torch.arange(g.n_rows, device=g.device, dtype=torch.int64),
+            g.rowptr[1:] - g.rowptr[:-1])
+        g._plans["_entry_rows"] = r
+    return r
+
+
+def _values(v: torch.Tensor, g: CsrGraph, name: str) -> torch.Tensor:
+    if v.dim() != 2 or v.shape[1] != g.nnz or v.shape[0] < 1:
+        raise ValueError(f"{name} must be [C, {g.nnz}] (got {tuple(v.shape)})")
+    return v
+
+
+def _product_shapes(mode, a, b, p):
+    if mode not in (0, 1):
+        raise ValueError("mode is 0 ((A . B) o P) or 1 ((A . B^T) o P)")
+    n, k = a.n_rows, a.n_cols
+    if mode == 0:
+        ok, m = b.n_rows == k, b.n_cols
+    else:
+        ok, m = b.n_cols == k, b.n_rows
+    if not ok or (p.n_rows, p.n_cols) != (n, m):
+        raise ValueError(f"shapes do not chain in mode {mode}: A [{a.n_rows}, {a.n_cols}], "
+                         f"B [{b.n_rows}, {b.n_cols}], P [{p.n_rows}, {p.n_cols}]")
+    return n, k, m
+
+
+def _segment_sum(terms: torch.Tensor, lengths: torch.Tensor) -> torch.Tensor:
+    """Sums of consecutive runs of ``terms`` [T, ...] along axis 0 (an empty run gives 0)."""
+    if lengths.numel() == 0 or terms.shape[0] == 0:
+        return terms.new_zeros((lengths.numel(),) + tuple(terms.shape[1:]))
+    return torch.segment_reduce(terms.contiguous(), "sum", lengths=lengths, axis=0, unsafe=True)
+
+
+def masked_product_torch(mode: int, a: CsrGraph, av: torch.Tensor, b: CsrGraph,
+                         bv: torch.Tensor, p: CsrGraph) -> torch.Tensor:
+    """``masked_product`` restated in torch ops (any device, any float dtype): the walked row
+    of every P entry expanded, each term's partner looked up with one ``searchsorted`` in the
+    searched operand's row-major keys, and the terms of an entry summed as one run. The CPU
+    path and the oracle of the kernel; its memory grows with the number of walked entries."""
+    n, k, m = _product_shapes(mode, a, b, p)
+    _values(av, a, "a values"), _values(bv, b, "b values")
+    dev = p.device
+    prow, pcol = _entry_rows(p), p.col.to(torch.int64)
+    wg, wv, lg, lv = (a, av, b, bv) if mode == 0 else (b, bv, a, av)
+    wrow = prow if mode == 0 else pcol
+    lo = wg.rowptr[wrow]
+    deg = wg.rowptr[wrow + 1] - lo
+    total = int(deg.sum()) if deg.numel() else 0
+    first = torch.cumsum(deg, 0) - deg
+    ent = torch.repeat_interleave(torch.arange(p.nnz, device=dev, dtype=torch.int64), deg)
+    q = torch.repeat_interleave(lo - first, deg) + torch.arange(total, device=dev,
+                                                                dtype=torch.int64)
+    wc = wg.col[q].to(torch.int64)
+    key = wc * lg.n_cols + pcol[ent] if mode == 0 else prow[ent] * lg.n_cols + wc
+    lkey = _entry_rows(lg) * lg.n_cols + lg.col.to(torch.int64)
+    if lkey.numel() > 1 and bool((lkey[1:] <= lkey[:-1]).any()):
+        raise IndexError("the searched operand's rows must ascend strictly")
+    if lkey.numel() == 0 or total == 0:
+        return av.new_zeros((av.shape[0], p.nnz))
+    pos = torch.searchsorted(lkey, key).clamp_(max=lkey.numel() - 1)
+    hit = lkey[pos] == key
+    term = torch.where(hit, wv[:, q] * lv[:, pos], torch.zeros((), dtype=av.dtype, device=dev))
+    return _segment_sum(term.t(), deg).t().contiguous()
+
+
+def _ws_product(lib, n, k, m, a, b, p, C, dev):
+    nbytes = int(lib.gnn_masked_product_workspace_bytes(n, k, m, a.nnz, b.nnz, p.nnz, C))
+    if nbytes < 0:
+        _lib.check(nbytes, "gnn_masked_product_workspace_bytes")
+    return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+
+def masked_product(mode: int, a: CsrGraph, av: torch.Tensor, b: CsrGraph, bv: torch.Tensor,
+                   p: CsrGraph, validate: bool = True) -> torch.Tensor:
+    """The values [C, nnz_p] of a sparse product on the pattern P (gnn_masked_product_f32).
+    mode 0: (A . B) o P with A [n, k] walked and B [k, m] searched; mode 1: (A . B^T) o P with
+    A [n, k] searched and B [m, k] walked. The searched operand's rows ascend strictly.
+    ``validate``: check the operands on the device first (one stream synchronisation); pass
+    False for patterns checked before. CPU operands run ``masked_product_torch``."""
+    n, k, m = _product_shapes(mode, a, b, p)
+    av, bv = _values(av, a, "a values"), _values(bv, b, "b values")
+    if av.shape[0] != bv.shape[0]:
+        raise ValueError("A and B carry the same number of channels")
+    if not av.is_cuda:
+        return masked_product_torch(mode, a, av, b, bv, p)
+    _require_device(av, bv, a.rowptr, b.rowptr, p.rowptr)
+    if av.dtype != torch.float32 or bv.dtype != torch.float32:
+        raise TypeError("masked_product takes float32 values")
+    C, dev = av.shape[0], av.device
+    if C > GTN_MAX_CHANNELS:
+        return torch.cat([masked_product(mode, a, av[c:c + 8], b, bv[c:c + 8], p,
+                                         validate and c == 0) for c in range(0, C, 8)])
+    av, bv = av.contiguous(), bv.contiguous()
+    out = torch.empty((C, p.nnz), dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    ws = _ws_product(lib, n, k, m, a, b, p, C, dev)
+    rc = _lib.invoke(
+        "gnn_masked_product_f32", mode=mode, a_rowptr=a.rowptr.data_ptr(),
+        a_col=_lib.ptr(a.col) if a.nnz else None, a_val=av.data_ptr() if a.nnz else None,
+        nnz_a=a.nnz, b_rowptr=b.rowptr.data_ptr(), b_col=_lib.ptr(b.col) if b.nnz else None,
+        b_val=bv.data_ptr() if b.nnz else None, nnz_b=b.nnz, p_rowptr=p.rowptr.data_ptr(),
+        p_col=_lib.ptr(p.col) if p.nnz else None, nnz_p=p.nnz, n=n, k=k, m=m, C=C,
+        out=out.data_ptr() if p.nnz else None, validate=int(bool(validate)),
+        workspace=ws.data_ptr(), workspace_bytes=ws.numel(), stream=_lib.stream_handle(dev))
+    if rc == _lib.E_ARG:
+        raise IndexError("masked_product: a column id out of range, a malformed rowptr or a "
+                         "searched row that does not ascend strictly")
+    _lib.check(rc, "gnn_masked_product_f32")
+    return out
+
+
+def _edge_rows_ok(F: int, *ts) -> bool:
+    """Whether the edge kernels take these feature rows: F % 4 == 0, 4 <= F <= 256, float32 on
+    the device (contiguous rows of such an F are 16-B aligned)."""
+    return F % 4 == 0 and 4 <= F <= 256 and all(t.is_cuda and t.dtype == torch.float32
+                                                for t in ts)
+
+
+def _offdiag(g: CsrGraph) -> torch.Tensor:
+    """bool [nnz]: the entries with row != col (cached on the graph)."""
+    mk = g._plans.get("_offdiag")
+    if mk is None:
+        mk = _entry_rows(g) != g.col.to(torch.int64)
+        g._plans["_offdiag"] = mk
+    return mk
+
+
+def edge_aggregate_torch(g: CsrGraph, v: torch.Tensor, x: torch.Tensor,
+                         skip_diag: bool = False) -> torch.Tensor:
+    """``edge_aggregate`` restated in torch ops: the terms v[c, e] x[.., col_e, :] of a row
+    summed as one run (any device, any float dtype)."""
+    _values(v, g, "v")
+    C = v.shape[0]
+    col = g.col.to(torch.int64)
+    rows = x[col][None] if x.dim() == 2 else x[:, col]                 # [1 | C, nnz, F]
+    vv = v * _offdiag(g) if skip_diag else v
+    term = (vv[:, :, None] * rows).permute(1, 0, 2)                     # [nnz, C, F]
+    out = _segment_sum(term, g.rowptr[1:] - g.rowptr[:-1])              # [n_rows, C, F]
+    return out.permute(1, 0, 2).contiguous().reshape(C, g.n_rows, x.shape[-1])
+
+
+def edge_aggregate(g: CsrGraph, v: torch.Tensor, x: torch.Tensor,
+                   skip_diag: bool = False) -> torch.Tensor:
+    """Y[c, r, :] = sum over e in row r, in CSR order, of v[c, e] X[col_e, :]
+    (gnn_edge_aggregate_f32): v [C, nnz]; x [n_cols, F] shared by the channels (each row
+    gathered once for all C outputs) or [C, n_cols, F] per channel. ``skip_diag`` leaves out
+    the entries with row == col. Shapes outside F % 4 == 0, 4 <= F <= 256 and CPU tensors run
+    ``edge_aggregate_torch``."""
+    _values(v, g, "v")
+    C, F = v.shape[0], x.shape[-1]
+    if x.shape[-2] != g.n_cols or (x.dim() == 3 and x.shape[0] != C) or x.dim() not in (2, 3):
+        raise ValueError(f"x must be [{g.n_cols}, F] or [{C}, {g.n_cols}, F] "
+                         f"(got {tuple(x.shape)})")
+    if not _edge_rows_ok(F, v, x):
+        return edge_aggregate_torch(g, v, x, skip_diag)
+    if C > GTN_MAX_CHANNELS:
+        return torch.cat([edge_aggregate(g, v[c:c + 8], x if x.dim() == 2 else x[c:c + 8],
+                                         skip_diag) for c in range(0, C, 8)])
+    v, x = v.contiguous(), x.contiguous()
+    y = torch.empty((C, g.n_rows, F), dtype=torch.float32, device=v.device)
+    _lib.run("gnn_edge_aggregate_f32", rowptr=g.rowptr.data_ptr(),
+             col=_lib.ptr(g.col) if g.nnz else None, val=v.data_ptr() if g.nnz else None,
+             nnz=g.nnz, n_rows=g.n_rows, n_cols=g.n_cols, X=x.data_ptr() if g.nnz else None,
+             ldx=F, x_stride=0 if x.dim() == 2 else g.n_cols, Y=y.data_ptr(), ldy=F, F=F, C=C,
+             skip_diag=int(bool(skip_diag)), stream=_lib.stream_handle(v.device))
+    return y
+
+
+def edge_dot_torch(g: CsrGraph, grad: torch.Tensor, x: torch.Tensor,
+                   skip_diag: bool = False) -> torch.Tensor:
+    """``edge_dot`` restated in torch ops (any device, any float dtype)."""
+    dv = (grad[:, _entry_rows(g)] * x[g.col.to(torch.int64)][None]).sum(-1)
+    return dv * _offdiag(g) if skip_diag else dv
+
+
+def edge_dot(g: CsrGraph, grad: torch.Tensor, x: torch.Tensor,
+             skip_diag: bool = False) -> torch.Tensor:
+    """dv[c, e] = <grad[c, row_e, :], x[col_e, :]> (gnn_edge_dot_f32), the edge-value adjoint
+    of ``edge_aggregate`` over a shared input: grad [C, n_rows, F], x [n_cols, F]; with
+    ``skip_diag`` the entries with row == col get 0. Other shapes and CPU tensors run
+    ``edge_dot_torch``."""
+    if grad.dim() != 3 or grad.shape[1] != g.n_rows or x.shape != (g.n_cols, grad.shape[2]):
+        raise ValueError(f"grad must be [C, {g.n_rows}, F] and x [{g.n_cols}, F] (got "
+                         f"{tuple(grad.shape)}, {tuple(x.shape)})")
+    C, F = grad.shape[0], grad.shape[2]
+    if not _edge_rows_ok(F, grad, x):
+        return edge_dot_torch(g, grad, x, skip_diag)
+    if C > GTN_MAX_CHANNELS:
+        return torch.cat([edge_dot(g, grad[c:c + 8], x, skip_diag) for c in range(0, C, 8)])
+    grad, x = grad.contiguous(), x.contiguous()
+    dv = torch.empty((C, g.nnz), dtype=torch.float32, device=grad.device)
+    if g.nnz:
+        _lib.run("gnn_edge_dot_f32", rowptr=g.rowptr.data_ptr(), col=g.col.data_ptr(), nnz=g.nnz,
+                 n_rows=g.n_rows, n_cols=g.n_cols, G=grad.data_ptr(), ldg=F, X=x.data_ptr(),
+                 ldx=F, dv=dv.data_ptr(), F=F, C=C, skip_diag=int(bool(skip_diag)),
+                 stream=_lib.stream_handle(grad.device))
+    return dv
+
+
+def edge_rowsum_torch(g: CsrGraph, v: torch.Tensor, skip_diag: bool = False) -> torch.Tensor:
+    """``edge_rowsum`` restated in torch ops (any device, any float dtype)."""
+    vv = v * _offdiag(g) if skip_diag else v
+    return _segment_sum(vv.t(), g.rowptr[1:] - g.rowptr[:-1]).t().contiguous()
+
+
+def edge_rowsum(g: CsrGraph, v: torch.Tensor, skip_diag: bool = False) -> torch.Tensor:
+    """d[c, r] = sum over e in row r, in CSR order, of v[c, e] (gnn_edge_rowsum_f32); over the
+    column view of a pattern these are the column sums of the reference's ``norm``."""
+    _values(v, g, "v")
+    if not (v.is_cuda and v.dtype == torch.float32):
+        return edge_rowsum_torch(g, v, skip_diag)
+    v = v.contiguous()
+    y = torch.empty((v.shape[0], g.n_rows), dtype=torch.float32, device=v.device)
+    _lib.run("gnn_edge_rowsum_f32", rowptr=g.rowptr.data_ptr(),
+             col=_lib.ptr(g.col) if g.nnz else None, val=v.data_ptr() if g.nnz else None,
+             nnz=g.nnz, n_rows=g.n_rows, C=v.shape[0], skip_diag=int(bool(skip_diag)),
+             y=y.data_ptr(), stream=_lib.stream_handle(v.device))
+    return y

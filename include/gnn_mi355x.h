@@ -1314,6 +1314,74 @@ int gnn_induced_subgraph_fill(const int64_t* rowptr, const int32_t* col, const f
                               int64_t nnz_c, int32_t* status, void* workspace,
                               int64_t workspace_bytes, void* stream);
 
+/* ---- Graph Transformer Network on CSR patterns (gtn.hip) ----
+ * The reference's GTN multiplies dense [C, N, N] stacks (GTN/models/GTLayer.py:25,30) and
+ * aggregates with a dense mm per channel (GTN/models/GTN.py:49-52). Here every matrix is a
+ * CSR pattern (int64 rowptr, int32 col) with C value sets over it, [C, nnz] channel-major
+ * contiguous fp32, 1 <= C <= 8 (else GNN_E_UNSUPPORTED). The structure of a product comes
+ * from gnn_relation_product_*; these entries compute VALUES. fp32 throughout, 64-bit offsets,
+ * no float atomics: every output element is written exactly once after a sum in a fixed
+ * order, so results are bit-identical from run to run.
+ *
+ * gnn_masked_product_f32: the values of a sparse product on a given pattern P [n, m]
+ * (p_rowptr, p_col; any column order within a row; out [C, nnz_p]).
+ *   mode 0  (A . B) o P, A [n, k] WALKED, B [k, m] SEARCHED:
+ *     out[c, (r, s)] = sum over q in A's row r, in stored order, of
+ *                      A[c, q] * B[c, find(B's row a_col[q], s)]
+ *   mode 1  (A . B^T) o P, A [n, k] SEARCHED, B [m, k] WALKED:
+ *     out[c, (r, s)] = sum over q in B's row s, in stored order, of
+ *                      B[c, q] * A[c, find(A's row r, b_col[q])]
+ *   find is a binary search in a row whose ids ascend strictly; a miss contributes nothing; a
+ *   P entry nothing contributes to is written as exactly 0.0f. Walked rows may come in any
+ *   order and may repeat an id: each stored entry contributes. The position found is used
+ *   for all C channels. The sum is a chain of fused multiply-adds in the walked row's stored
+ *   order whichever class handles the entry.
+ *   Classes, by the walked row's length (gnn_masked_product_class_limits): up to *lane_max
+ *   entries the P entry's own lane walks the row; longer rows are taken by the whole
+ *   wavefront, *wave_chunk walked entries at a time, and the hits added in stored order.
+ *   validate != 0: rowptrs, id ranges (A's and mode 1's B's ids < k, mode 0's B's and P's
+ *   ids < m) and the strict ascent of the searched operand's rows are checked on the device
+ *   first and `stream` is SYNCHRONISED once; a failure returns GNN_E_ARG, nothing is read
+ *   through the operands and a later valid call works. validate == 0 trusts operands
+ *   validated before (cached patterns) and does not synchronise.
+ *   Workspace: gnn_masked_product_workspace_bytes(...) bytes, a function of the shapes alone.
+ *   Limits: n, k, m < 2^31 - 1 (GNN_E_UNSUPPORTED); negative sizes, null operands, a short
+ *   workspace, a mode outside {0, 1} -> GNN_E_ARG.
+ *
+ * gnn_edge_aggregate_f32: Y[c, r, :] = sum over e in row r, in CSR order, of
+ *   val[c, e] * X[c * x_stride + col[e], :]; Y [C, n_rows, ldy]. x_stride == 0 shares one
+ *   input [n_cols, ldx] among the channels (each row gathered once for all C outputs), else
+ *   x_stride >= n_cols rows lie between the channels' inputs. skip_diag != 0 leaves out the
+ *   edges with col[e] == r (no masked copy of the values is made).
+ * gnn_edge_dot_f32: dv[c, e] = <G[c, row(e), :], X[col[e], :]> (G [C, n_rows, ldg]), the
+ *   edge-value adjoint of the aggregate over a shared input; skip_diag != 0 writes 0.0f for
+ *   col[e] == row(e). A lane group per edge, a fixed xor-shuffle sum.
+ *   Both: F % 4 == 0, 4 <= F <= 256 (else GNN_E_UNSUPPORTED), pitches >= F, multiples of 4,
+ *   bases 16-byte aligned (else GNN_E_ALIGN). Column ids are trusted (a CsrGraph's).
+ * gnn_edge_rowsum_f32: y[c, r] = sum over e in row r, in CSR order, of val[c, e]
+ *   (y [C, n_rows]; skip_diag as above): the column sums of the reference's norm when run
+ *   over the column view.
+ */
+int64_t gnn_masked_product_workspace_bytes(int64_t n, int64_t k, int64_t m, int64_t nnz_a,
+                                           int64_t nnz_b, int64_t nnz_p, int C);
+int gnn_masked_product_class_limits(int64_t* lane_max, int64_t* wave_chunk);
+int gnn_masked_product_f32(int mode, const int64_t* a_rowptr, const int32_t* a_col,
+                           const float* a_val, int64_t nnz_a, const int64_t* b_rowptr,
+                           const int32_t* b_col, const float* b_val, int64_t nnz_b,
+                           const int64_t* p_rowptr, const int32_t* p_col, int64_t nnz_p,
+                           int64_t n, int64_t k, int64_t m, int C, float* out, int validate,
+                           void* workspace, int64_t workspace_bytes, void* stream);
+int gnn_edge_aggregate_f32(const int64_t* rowptr, const int32_t* col, const float* val,
+                           int64_t nnz, int64_t n_rows, int64_t n_cols, const float* X,
+                           int64_t ldx, int64_t x_stride, float* Y, int64_t ldy, int64_t F,
+                           int C, int skip_diag, void* stream);
+int gnn_edge_dot_f32(const int64_t* rowptr, const int32_t* col, int64_t nnz, int64_t n_rows,
+                     int64_t n_cols, const float* G, int64_t ldg, const float* X, int64_t ldx,
+                     float* dv, int64_t F, int C, int skip_diag, void* stream);
+int gnn_edge_rowsum_f32(const int64_t* rowptr, const int32_t* col, const float* val,
+                        int64_t nnz, int64_t n_rows, int C, int skip_diag, float* y,
+                        void* stream);
+
 /* ---- CPython-exact host sampler (pysample.cpp; host memory, no stream) ----
  * Bit-exact restatement of the reference's host-side GraphSAGE sampling, which draws
  * from CPython's global `random` and iterates Python sets:
