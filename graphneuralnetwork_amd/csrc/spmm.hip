@@ -112,3 +112,23 @@ extern "C" int gnn_spmm_csr_tasks_f32(const int64_t* rowptr, const int32_t* col,
                     mid_row, n_mid, partial, flags, stream, xh, ldh,
                     task_row != nullptr ? task_row : mid_row, n_task);
 }
+
+// ---- pass 1 of the XCD-sliced direct form (GCN/GCN.py:43-45, same aggregation): one wave per
+// item, the edge stream in scalar registers (spmm_items_kernel) ----
+extern "C" int gnn_spmm_items_f32(const int64_t* rowptr, const int32_t* col, const float* val,
+                                  int64_t n_pos, const float* x, int64_t ldx, int64_t feat,
+                                  float* part, int64_t ldp, void* stream) {
+  if (n_pos < 0 || feat < 0 || ldx < feat || ldp < feat) return GNN_E_ARG;
+  if (rowptr == nullptr || x == nullptr || part == nullptr) return GNN_E_ARG;
+  if (n_pos > 0 && (col == nullptr || val == nullptr)) return GNN_E_ARG;
+  if (feat != 128 && feat != 256) return GNN_E_UNSUPPORTED;
+  if (ldx % 4 != 0 || ldp % 4 != 0 || !aligned_to(x, 16) || !aligned_to(part, 16))
+    return GNN_E_UNSUPPORTED;  // 16 B per lane
+  if (ldx > 0xffffffffLL) return GNN_E_UNSUPPORTED;  // col * ldx: a 32 x 32 -> 64 bit product
+  if ((n_pos + kWavesPerBlock - 1) / kWavesPerBlock > 0x7fffffffLL) return GNN_E_UNSUPPORTED;
+  if (n_pos == 0) return GNN_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  // lanes per row: at 128 columns a wave instruction gathers two rows
+  return feat == 128 ? launch_spmm_items<32>(rowptr, col, val, n_pos, x, ldx, part, ldp, s)
+                     : launch_spmm_items<64>(rowptr, col, val, n_pos, x, ldx, part, ldp, s);
+}

@@ -606,6 +606,145 @@ __global__ __launch_bounds__(kBlock) void spmm_csr_kernel(SpmmParamsT<XT, HT> P)
   }
 }
 
+// Edges per batch of spmm_items_kernel, their rows in flight at once, by lanes per row: 16 at
+// LPR = 32 (F = 128), 8 at LPR = 64 (F = 256, where 16 would take 78 VGPRs and leave 6 waves
+// per SIMD for a difference that cannot be told from the run-to-run spread). -DGNN_SPMM_ITEMS_U=n
+// sets both (tools/spmm_items_ab.py --variants iu8,iu16; DESIGN.md sections 5.20 and 6).
+constexpr int items_u(int lpr) {
+#ifdef GNN_SPMM_ITEMS_U
+  return GNN_SPMM_ITEMS_U;
+#else
+  return lpr == 32 ? 16 : 8;
+#endif
+}
+
+// Plan data (rowptr, col, val) read at wave-uniform indices: through the constant address
+// space such a read is a scalar load, and what it returns lives in SGPRs. The kernel never
+// writes these arrays; the scalar cache is invalidated between kernels, so a caller may
+// rewrite them between launches.
+template <typename T>
+using ConstPtr = const T __attribute__((address_space(4)))*;
+template <typename T>
+__device__ __forceinline__ ConstPtr<T> const_ptr(const T* p) {
+  return (ConstPtr<T>)(p);
+}
+
+// acc += the K edges from e on of one item (spmm_items_kernel): the K (col, val) pairs by scalar
+// loads, all K / EPI row loads issued (EPI = 64 / LPR rows per wave instruction, 16 B per lane),
+// then the FMAs in edge order. With two slots (LPR = 32) the low half of the wave takes edges
+// e, e + 2, ..., the high half e + 1, e + 3, ... (K is even). The two row offsets of a pair
+// are scalars; a lane of the high half reaches its row by adding their difference under its
+// mask hm (all ones there, zero in the low half): two ANDs instead of a 64-bit multiply per
+// lane, which a select between the two column ids would leave the compiler with.
+template <int LPR, int K>
+__device__ __forceinline__ void items_batch(ConstPtr<int32_t> cs, ConstPtr<float> vs, int64_t e,
+                                            const float* xs, uint32_t ldx, uint64_t hm, f4& acc) {
+  constexpr int EPI = kWave / LPR;
+  static_assert(K % EPI == 0, "whole wave instructions");
+  uint32_t c[K];
+  float w[K];
+  f4 xv[K / EPI];
+#pragma unroll
+  for (int u = 0; u < K; ++u) {
+    c[u] = static_cast<uint32_t>(cs[e + u]);
+    w[u] = vs[e + u];
+  }
+#pragma unroll
+  for (int j = 0; j < K / EPI; ++j) {
+    uint64_t off = static_cast<uint64_t>(c[j * EPI]) * ldx;
+    if constexpr (EPI == 2) off += hm & (static_cast<uint64_t>(c[j * EPI + 1]) * ldx - off);
+    xv[j] = vload<4>(xs + off);
+  }
+#pragma unroll
+  for (int j = 0; j < K / EPI; ++j) {
+    float wl = w[j * EPI];
+    if constexpr (EPI == 2) wl = hm ? w[j * EPI + 1] : wl;
+    acc += wl * xv[j];
+  }
+}
+// n edges from e on, n a multiple of STEP in [LO, HI]: one straight-line batch of exactly n
+// edges, picked by scalar compares (a tail cut into pieces would wait for memory once per piece)
+template <int LPR, int LO, int HI, int STEP>
+__device__ __forceinline__ void items_tail(int n, ConstPtr<int32_t> cs, ConstPtr<float> vs,
+                                           int64_t e, const float* xs, uint32_t ldx, uint64_t hm,
+                                           f4& acc) {
+  if constexpr (LO >= HI) {
+    items_batch<LPR, LO>(cs, vs, e, xs, ldx, hm, acc);
+  } else {
+    constexpr int M = (LO + HI) / (2 * STEP) * STEP;  // LO <= M < HI
+    if (n <= M)
+      items_tail<LPR, LO, M, STEP>(n, cs, vs, e, xs, ldx, hm, acc);
+    else
+      items_tail<LPR, M + STEP, HI, STEP>(n, cs, vs, e, xs, ldx, hm, acc);
+  }
+}
+
+// Pass 1 of the XCD-sliced direct form: part[pos] = sum_{e in item pos} val[e] * x[col[e]].
+// An item is a short run of edges (2 .. the plan's chunk) whose columns are plain rows of X,
+// and its partial row has no epilogue, so one wave streams the item with its edge loop in
+// scalar registers: (col, val) come in by scalar loads and the 64-bit row offset col * ldx is
+// scalar arithmetic. The lanes are laid out as in gather_rows, 16 B per lane: LPR = feat / 4
+// lanes hold a row, so at F = 128 a wave instruction gathers two rows (edge slots) and at
+// F = 256 one. Full batches of U edges, then one batch of exactly the edges that are left
+// (with two slots: of the even part, then the last odd edge in the low slot alone): no lane
+// predicate in the loop, and nothing is read past col[end).
+//
+// The sums are those of gather_rows with reduce_slots on the same item, bit for bit: slot g
+// adds the edges at distance g, g + EPI, ... from the item's first edge in ascending order,
+// and the row is slot 0 + slot 1.
+template <int LPR, int U>
+__global__ __launch_bounds__(kBlock) void spmm_items_kernel(
+    const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
+    const float* __restrict__ val, int64_t n_pos, const float* __restrict__ x, uint32_t ldx,
+    float* __restrict__ part, int64_t ldp) {
+  constexpr int EPI = kWave / LPR;
+  static_assert((LPR == 32 || LPR == 64) && U % 2 == 0, "one or two slots, whole pairs");
+  const int lane = threadIdx.x & (kWave - 1);
+  const int sub = lane & (LPR - 1);
+  const bool hi = lane >= LPR;
+  // all ones in the lanes of the high slot (bit 5 of the lane spread by the shifts, so that it
+  // stays a mask and the row offsets stay scalars)
+  const int hbit = static_cast<int>(static_cast<uint32_t>(lane) << 26) >> 31;
+  const uint64_t hm = EPI == 2 ? static_cast<uint64_t>(static_cast<int64_t>(hbit)) : 0;
+  // (the compiler cannot see that threadIdx.x >> 6 is the same in every lane)
+  const int64_t pos = wave_uniform(static_cast<int64_t>(blockIdx.x) * kWavesPerBlock +
+                                   static_cast<int64_t>(threadIdx.x >> 6));
+  if (pos >= n_pos) return;
+  const ConstPtr<int64_t> rp = const_ptr(rowptr);
+  const ConstPtr<int32_t> cs = const_ptr(col);
+  const ConstPtr<float> vs = const_ptr(val);
+  int64_t e = rp[pos];
+  const int64_t end = rp[pos + 1];
+  const float* xs = x + sub * 4;
+  f4 acc = vzero<4>();
+  for (; end - e >= U; e += U) items_batch<LPR, U>(cs, vs, e, xs, ldx, hm, acc);
+  const int n = static_cast<int>(end - e);  // 0 .. U - 1
+  const int whole = n & ~(EPI - 1);
+  if (whole > 0) items_tail<LPR, EPI, U - EPI, EPI>(whole, cs, vs, e, xs, ldx, hm, acc);
+  if constexpr (EPI == 2) {
+    if (n & 1) {  // the last edge of an odd item: slot 0 only, as the masked slot of gather_rows
+      const float* xr = xs + static_cast<uint64_t>(static_cast<uint32_t>(cs[end - 1])) * ldx;
+      if (!hi) acc += vs[end - 1] * vload<4>(xr);
+    }
+    acc += shfl_xor_f(acc, LPR);
+  }
+  if (!hi) nt_store<4>(part + pos * ldp + sub * 4, acc);
+}
+
+// feat = 128 or 256 exactly, ldx / ldp multiples of 4, ldx < 2^32, x / part 16-B aligned:
+// checked by the entry (gnn_spmm_items_f32).
+template <int LPR>
+static int launch_spmm_items(const int64_t* rowptr, const int32_t* col, const float* val,
+                             int64_t n_pos, const float* x, int64_t ldx, float* part, int64_t ldp,
+                             hipStream_t stream) {
+  const int64_t blocks = (n_pos + kWavesPerBlock - 1) / kWavesPerBlock;
+  if (blocks > 0x7fffffffLL) return GNN_E_UNSUPPORTED;
+  hipLaunchKernelGGL((spmm_items_kernel<LPR, items_u(LPR)>), dim3(static_cast<unsigned>(blocks)),
+                     dim3(kBlock), 0, stream, rowptr, col, val, n_pos, x,
+                     static_cast<uint32_t>(ldx), part, ldp);
+  return launch_status();
+}
+
 // y[long_row[i]] = act(sum_{s in segs(i)} partial[s] + bias).
 // One workgroup (4 waves x EPI slots) per long row, UF partial-row loads in flight
 // per slot, so a 1,460-segment hub row is not a serial tail; the slot / wave

@@ -106,6 +106,11 @@ XCD_SMALL_ITEM = None
 # on a degree-ordered graph (graph.degree_order) the hub rows are X's first rows: read them
 # in place instead of copying them into a staged table (XcdHubPlan.prefix / direct)
 XCD_DIRECT = True
+# pass 1 of that direct form on gnn_spmm_items_f32 (one wave per item, the edge stream in
+# scalar registers) where the entry covers the call: fp32 X of 128 or 256 columns on the
+# 16-B vector path. Same partial rows bit for bit; A/B: tools/spmm_items_ab.py, DESIGN.md
+# section 5.20.
+SPMM_ITEMS_KERNEL = True
 # bf16 rows (spmm_forward with a bfloat16 X): whether the default policy (``xcd=None``) takes
 # the XCD-sliced direct form at all. Off: measured in one process at cfg2 on the
 # column-ordered graph (tools/spmm_bf16_ab.py), the hub rows read in
@@ -575,18 +580,35 @@ def model_dropout(x: torch.Tensor, p: float, training: bool, perm=None, inv=None
     return DropoutRows.apply(x, p, dropout_seed(), perm, inv)
 
 
+def _spmm_items_call(items: CsrGraph, x, feat, part, stream) -> bool:
+    """Pass 1 on gnn_spmm_items_f32. False (nothing launched) when the switch is off or the
+    entry does not cover the call -- bf16 rows, another width, an odd pitch or alignment: the
+    caller then runs the plain kernel."""
+    if not SPMM_ITEMS_KERNEL or x.dtype != torch.float32:
+        return False
+    rc = _lib.invoke("gnn_spmm_items_f32", rowptr=items.rowptr.data_ptr(),
+                     col=items.col.data_ptr(), val=items.val.data_ptr(), n_pos=items.n_rows,
+                     x=x.data_ptr(), ldx=x.stride(0), feat=feat, part=part.data_ptr(),
+                     ldp=part.stride(0), stream=stream)
+    if rc == _lib.E_UNSUPPORTED:
+        return False
+    _lib.check(rc, "gnn_spmm_items_f32")
+    return True
+
+
 def _spmm_xcd_direct(xp, x, feat, bias, out, seg, skip_empty, flags, stream):
     """The XCD-sliced SpMM of a degree-ordered graph (graph.degree_order): the hub rows are
-    X's first k rows, so there is no staging copy. Pass 1 (plain kernel) reads the items'
-    hub rows from X into a partial-row buffer; pass 2 reads X and that buffer (c < 0 ->
-    partial row -1-c). The partial rows are fp32 for a bf16 X too (the bf16 hub / tasks
-    entries with an fp32 xh)."""
+    X's first k rows, so there is no staging copy. Pass 1 (the items kernel, or the plain
+    kernel where that does not apply) reads the items' hub rows from X into a partial-row
+    buffer; pass 2 reads X and that buffer (c < 0 -> partial row -1-c). The partial rows are
+    fp32 for a bf16 X too (the bf16 hub / tasks entries with an fp32 xh)."""
     items, rest = xp.direct()
     part = torch.empty((xp.n_pos, feat), dtype=torch.float32, device=x.device)
     p1 = items.plan(seg)
     if p1.n_seg or p1.n_small:
         raise RuntimeError("XCD hub plan: item rows outside the mid-row class")
-    _spmm_plain_call(items, p1, False, x, feat, None, part, feat, None, 0, stream)
+    if not _spmm_items_call(items, x, feat, part, stream):
+        _spmm_plain_call(items, p1, False, x, feat, None, part, feat, None, 0, stream)
     if _tasks_ok(feat, x, out, bias, part):
         tp = rest.task_plan(seg, TASK_MAX_DEG, _task_cost(feat))
         partial = None

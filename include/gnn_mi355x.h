@@ -206,6 +206,26 @@ int gnn_spmm_tasks_check(const int32_t* task_row, int64_t n_task, int64_t n_rows
                          void* stream);
 
 /*
+ * Pass 1 of the XCD-sliced aggregation over a degree-ordered graph (same call site,
+ * GCN/GCN.py:43-45): part[p, :] = sum_{e in [rowptr[p], rowptr[p+1])} val[e] * x[col[e], :] for
+ * the n_pos item positions of the plan, with no bias, activation or accumulate. One wavefront
+ * per position (position 4b + w is wave w of workgroup b, as gnn_spmm_csr_f32 places its mid
+ * rows), the edge stream held in scalar registers: rowptr / col / val are read by scalar loads
+ * and never written, every col[e] is a plain row of x (0 <= col[e], not range-checked, as in
+ * the other entries), nothing is read past col[rowptr[n_pos]). The sums are bit-identical to
+ * gnn_spmm_csr_f32's on the same CSR with every row in the mid-row class.
+ * Covers fp32 rows of feat == 128 or 256 only, 16 B per lane (feat / 4 lanes hold a row, so a
+ * wave instruction gathers two rows at 128 columns): ldx and ldp multiples of 4, ldx < 2^32,
+ * x and part 16-B aligned, at most 2^31 - 1 workgroups; any other shape returns
+ * GNN_E_UNSUPPORTED (the caller runs gnn_spmm_csr_f32). NULL rowptr / x / part (col /
+ * val with n_pos > 0), a negative size or ldx / ldp < feat: GNN_E_ARG. n_pos == 0: GNN_OK,
+ * nothing launched.
+ */
+int gnn_spmm_items_f32(const int64_t* rowptr, const int32_t* col, const float* val, int64_t n_pos,
+                       const float* x, int64_t ldx, int64_t feat, float* part, int64_t ldp,
+                       void* stream);
+
+/*
  * In-degree of every column of a CSR (deg[c] = number of entries with column c, uint32,
  * device), the histogram of gnn_hub_plan_build: LDS-privatised counts for the hottest ids, so
  * the hub columns' counters do not serialise. A column id outside [0, n_cols) sets

@@ -1,12 +1,14 @@
 """Register record of the SpMM kernels: compiles spmm.hip and spmm_bf16.hip for gfx950 with
 -Rpass-analysis=kernel-resource-usage (device side only, no GPU needed) and prints VGPRs,
-SGPRs, scratch and occupancy of every instantiated spmm_csr_kernel / spmm_fixup_kernel.
+SGPRs, scratch and occupancy of every instantiated spmm_csr_kernel / spmm_items_kernel /
+spmm_fixup_kernel.
 
     python tools/kernel_resources.py [-D GNN_SPMM_TASK_U=8 ...] [--all] [--out FILE]
 
 The template arguments of spmm_csr_kernel are <VW, LPR, NCH, U, NT, HUB, TASKS, CPL, XT, HT>;
 the flagship pass 2 (fp32, F = 128, packed tasks over hub ids) is
-<4, 32, 1, 4, true, true, true, 1, float, float>.
+<4, 32, 1, 4, true, true, true, 1, float, float>; those of spmm_items_kernel (pass 1 under
+ops.SPMM_ITEMS_KERNEL) are <LPR, U>: <32, 16> at F = 128, <64, 8> at F = 256.
 """
 import argparse
 import re

@@ -67,6 +67,11 @@ VARIANTS = {
     "sbu4": ["GNN_SAGE_BF16_U=4"],
     "sbu8": ["GNN_SAGE_BF16_U=8"],
     "sbu16": ["GNN_SAGE_BF16_U=16"],
+    # edges per batch in spmm_items_kernel (pass 1 of the XCD-direct form; the A/B runs in
+    # tools/spmm_items_ab.py --variants, which also flips ops.SPMM_ITEMS_KERNEL); the default is
+    # 16 at F = 128 and 8 at F = 256
+    "iu8": ["GNN_SPMM_ITEMS_U=8"],
+    "iu16": ["GNN_SPMM_ITEMS_U=16"],
 }
 
 
