@@ -12,6 +12,8 @@ state_dict keys as the reference):
                                           backward lines of the train_eval.py loops
 * ``graphneuralnetwork_amd.gtn``       -- GTConv, GTLayer, GTN_Model, norm  (GTN/models/*.py);
                                           also importable from the package itself
+* ``graphneuralnetwork_amd.gatne``     -- GraphEncoder, GraphDecoder, GATNEModel, SigmoidBCELoss,
+                                          ValScale                     (GATNE_Pytorch/models/GATNE.py)
 
 The aggregation hot paths run as hand-written gfx950 HIP kernels in
 ``lib/libgnn_mi355x.so`` behind the C-ABI of ``include/gnn_mi355x.h``.

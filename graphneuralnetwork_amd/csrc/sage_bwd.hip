@@ -561,10 +561,11 @@ extern "C" int64_t gnn_sage_scatter_agg_maxpool_workspace_bytes(int64_t M, int64
   return gnn_sage_scatter_agg_workspace_bytes(M, k, feat);  // the MEAN scatter's layout
 }
 
-extern "C" int gnn_sage_scatter_agg_f32(const float* dbuf, int64_t ldd, const int64_t* ptr,
-                                        const int32_t* slot, int64_t M, int64_t k, int64_t feat,
-                                        int64_t n_prev, float* dx, int64_t ldx, void* workspace,
-                                        int64_t workspace_bytes, void* stream) {
+// the body of gnn_sage_scatter_agg_f32 and its scaled twin: `scale` multiplies every slot's row
+static int sb_scatter_agg(const float* dbuf, int64_t ldd, const int64_t* ptr, const int32_t* slot,
+                          int64_t M, int64_t k, int64_t feat, int64_t n_prev, float* dx,
+                          int64_t ldx, float scale, void* workspace, int64_t workspace_bytes,
+                          void* stream) {
   if (M < 0 || k < 0 || feat < 0 || n_prev < 0) return GNN_E_ARG;
   if (!ptr || !workspace || (n_prev > 0 && !dx) || (M > 0 && (!dbuf || !slot))) return GNN_E_ARG;
   const int64_t n = sb_slots_nbr(M, k);
@@ -577,9 +578,29 @@ extern "C" int gnn_sage_scatter_agg_f32(const float* dbuf, int64_t ldd, const in
       !aligned_to(workspace, 16))
     return GNN_E_ALIGN;
   if (n_prev == 0) return GNN_OK;
-  SbAggArgs a{{dbuf, ldd, ptr, slot, M, k, n_prev, n, k > 0 ? 1.0f / static_cast<float>(k) : 0.f,
-               dx, ldx, w.count, w.longs, w.tasks, w.part, w.max_long, w.max_tasks}};
+  SbAggArgs a{{dbuf, ldd, ptr, slot, M, k, n_prev, n, scale, dx, ldx, w.count, w.longs, w.tasks,
+               w.part, w.max_long, w.max_tasks}};
   return dispatch_sage_scatter(a, feat, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int gnn_sage_scatter_agg_f32(const float* dbuf, int64_t ldd, const int64_t* ptr,
+                                        const int32_t* slot, int64_t M, int64_t k, int64_t feat,
+                                        int64_t n_prev, float* dx, int64_t ldx, void* workspace,
+                                        int64_t workspace_bytes, void* stream) {
+  return sb_scatter_agg(dbuf, ldd, ptr, slot, M, k, feat, n_prev, dx, ldx,
+                        k > 0 ? 1.0f / static_cast<float>(k) : 0.f, workspace, workspace_bytes,
+                        stream);
+}
+
+// the factor given by the caller (1 for a SUM over the neighbours or a row gather, k = 1)
+extern "C" int gnn_sage_scatter_agg_scaled_f32(const float* dbuf, int64_t ldd, const int64_t* ptr,
+                                               const int32_t* slot, int64_t M, int64_t k,
+                                               int64_t feat, int64_t n_prev, float* dx,
+                                               int64_t ldx, float scale, void* workspace,
+                                               int64_t workspace_bytes, void* stream) {
+  if (k < 1) return k < 0 ? GNN_E_ARG : GNN_E_UNSUPPORTED;
+  return sb_scatter_agg(dbuf, ldd, ptr, slot, M, k, feat, n_prev, dx, ldx, scale, workspace,
+                        workspace_bytes, stream);
 }
 
 extern "C" int gnn_sage_scatter_agg_maxpool_f32(const float* dbuf, int64_t ldd, const uint8_t* arg,

@@ -2011,8 +2011,9 @@ def sage_maps_transpose_nbr(neigh_idx: torch.Tensor, n_prev: int,
     return SageMapsT(ptr, slot, M, k, False)
 
 
-def _scatter_agg(dbuf, arg, tr, n_prev, out):
-    """``sage_scatter_agg`` (arg None) / ``sage_scatter_agg_maxpool``."""
+def _scatter_agg(dbuf, arg, tr, n_prev, out, scale=None):
+    """``sage_scatter_agg`` (arg None; ``scale`` given: the scaled entry) /
+    ``sage_scatter_agg_maxpool``."""
     _require_device(dbuf, arg, tr.ptr, tr.slot, out)
     if dbuf.dtype != torch.float32:
         raise TypeError(f"dbuf must be float32 (got {dbuf.dtype})")
@@ -2054,7 +2055,12 @@ def _scatter_agg(dbuf, arg, tr, n_prev, out):
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dbuf.device)
     ptr, slot = tr.ptr.contiguous(), tr.slot.contiguous()
     ldd = dbuf.stride(0) if M > 1 else F
-    if arg is None:
+    if arg is None and scale is not None:
+        _lib.run("gnn_sage_scatter_agg_scaled_f32", dbuf=dbuf.data_ptr(), ldd=ldd,
+                 ptr=ptr.data_ptr(), slot=slot.data_ptr(), M=M, k=k, feat=F, n_prev=n_prev,
+                 dx=dx.data_ptr(), ldx=F, scale=float(scale), workspace=ws.data_ptr(),
+                 workspace_bytes=ws.numel(), stream=_lib.stream_handle(dbuf.device))
+    elif arg is None:
         _lib.check(lib.gnn_sage_scatter_agg_f32(
             dbuf.data_ptr(), ldd, ptr.data_ptr(), slot.data_ptr(), M, k, F, n_prev, dx.data_ptr(),
             F, ws.data_ptr(), ws.numel(), _lib.stream_handle(dbuf.device)),
@@ -2068,7 +2074,8 @@ def _scatter_agg(dbuf, arg, tr, n_prev, out):
 
 
 def sage_scatter_agg(dbuf: torch.Tensor, tr: SageMapsT, n_prev: int,
-                     out: torch.Tensor | None = None) -> torch.Tensor | None:
+                     out: torch.Tensor | None = None,
+                     scale: float | None = None) -> torch.Tensor | None:
     """The adjoint of ``sage_gather_aggregate(table, idx, 'MEAN')`` (gnn_sage_scatter_agg_f32):
     dX[t] = sum of dbuf[m] / k over the entries (m, j) with idx[m, j] == t, for the maps
     ``tr = sage_maps_transpose_nbr(idx, n_prev)``; float32 [n_prev, F] with F = dbuf.shape[1].
@@ -2076,8 +2083,11 @@ def sage_scatter_agg(dbuf: torch.Tensor, tr: SageMapsT, n_prev: int,
     nobody references are zeros, fp32 sums in slot order, no float atomics, bit-identical from
     run to run; ``dbuf`` any float32 [M, F] view with 16-B aligned rows, ``out`` a contiguous
     float32 [n_prev, F] tensor to write. None where the kernel does not take the shape (F not a
-    power of two in [4, 256], k = 0, a misaligned view)."""
-    return _scatter_agg(dbuf, None, tr, n_prev, out)
+    power of two in [4, 256], k = 0, a misaligned view).
+    ``scale``: the factor in place of 1 / k (gnn_sage_scatter_agg_scaled_f32): 1 for the adjoint
+    of a SUM over the neighbours or of a row gather (k = 1); ``scale = 1 / k`` (in float32) gives
+    the default's result bit for bit."""
+    return _scatter_agg(dbuf, None, tr, n_prev, out, scale)
 
 
 def sage_scatter_agg_maxpool(dbuf: torch.Tensor, arg: torch.Tensor, tr: SageMapsT, n_prev: int,
@@ -3060,3 +3070,169 @@ def edge_rowsum(g: CsrGraph, v: torch.Tensor, skip_diag: bool = False) -> torch.
              nnz=g.nnz, n_rows=g.n_rows, C=v.shape[0], skip_diag=int(bool(skip_diag)),
              y=y.data_ptr(), stream=_lib.stream_handle(v.device))
     return y
+
+
+# ---------------------------------------------------------------- GATNE (csrc/gatne.hip)
+def gatne_supported(E: int, U: int, A: int, T: int) -> bool:
+    """Whether the GATNE attention kernels take the widths (gnn_gatne_supported, the one source
+    of the set): U, A in {16, 32, 64, 128}, E a power of two in [16, 256], 1 <= T <= 8."""
+    return bool(_lib.load().gnn_gatne_supported(int(E), int(U), int(A), int(T)))
+
+
+def typed_gather_sum(table: torch.Tensor, nbr: torch.Tensor, agg_func: str = "SUM",
+                     check: bool = True) -> torch.Tensor:
+    """u[b, t] = sum (``'SUM'``) or mean (``'MEAN'``) over k of the rows ``nbr[b, t, k]`` of
+    ``table`` (gnn_typed_gather_sum_f32): ``table`` [N, T, W] is read at type t (GATNE's
+    ``node_type_embeddings``), ``table`` [N, W] the same row for every type (a feature table).
+    nbr: int64 [B, T, K]; W a multiple of 4; float32 [B, T, W], fp32 sums in k order. An id
+    outside [0, N) is skipped: ``check`` raises IndexError for it (one host read)."""
+    if agg_func not in ("SUM", "MEAN"):
+        raise ValueError("please choice else aggregator!")
+    _require_device(table, nbr)
+    if table.dtype != torch.float32:
+        raise TypeError(f"table must be float32 (got {table.dtype})")
+    if nbr.dim() != 3 or table.dim() not in (2, 3):
+        raise ValueError("nbr must be [B, T, K] and table [N, T, W] or [N, W]")
+    B, T, K = nbr.shape
+    if table.dim() == 3 and table.shape[1] != T:
+        raise ValueError(f"table holds {table.shape[1]} types, nbr {T}")
+    W = table.shape[-1]
+    if W % 4:
+        raise ValueError(f"the row width must be a multiple of 4 (got {W})")
+    if not table.is_contiguous() or table.data_ptr() % 16:
+        table = table.clone(memory_format=torch.contiguous_format)
+    nbr = nbr.to(torch.int64).contiguous()
+    u = torch.empty((B, T, W), dtype=torch.float32, device=table.device)
+    if B == 0 or T == 0 or W == 0:
+        return u
+    if K == 0:
+        if agg_func == "MEAN":
+            _empty_reduction(0)
+        return u.fill_(float("nan") if agg_func == "MEAN" else 0.0)
+    err = _err_flag(table.device, check)
+    ld_n, ld_t = (T * W, W) if table.dim() == 3 else (W, 0)
+    _lib.run("gnn_typed_gather_sum_f32", table=table.data_ptr(), ld_n=ld_n, ld_t=ld_t,
+             n_table=table.shape[0], nbr=nbr.data_ptr(), B=B, T=T, K=K, W=W,
+             scale=1.0 if agg_func == "SUM" else 1.0 / K, u=u.data_ptr(), ldu=W,
+             err_flag=err.data_ptr(), stream=_lib.stream_handle(table.device))
+    if check:
+        _check_err(err, "typed_gather_sum")
+    return u
+
+
+class GatneOrder(NamedTuple):
+    """Rows sorted by edge type (``gatne_order``): ``perm`` int32 [B] (the batch row at every
+    sorted position), ``seg`` int32 [T + 2] (seg[t] = the first position of a type >= t;
+    seg[T] .. seg[T + 1] = B are the rows of no type)."""
+    perm: torch.Tensor
+    seg: torch.Tensor
+    T: int
+
+
+def gatne_order(types: torch.Tensor, T: int, check: bool = True) -> GatneOrder:
+    """The stable order of the batch rows by edge type (gnn_gatne_order): ``perm`` is exactly
+    numpy's stable argsort of ``types`` and ``seg[:T + 1]`` its bincount / cumsum. A type outside
+    [0, T) sorts last; ``check`` raises IndexError for it (one host read), unchecked such rows
+    come out of the attention stage as NaN."""
+    _require_device(types)
+    if types.dim() != 1:
+        raise ValueError("types must be [B]")
+    T = int(T)
+    types = types.to(torch.int64).contiguous()
+    B = types.numel()
+    dev = types.device
+    lib = _lib.load()
+    nbytes = int(lib.gnn_gatne_order_workspace_bytes(B, T))
+    if nbytes < 0:
+        raise ValueError(f"gatne_order does not take B={B}, T={T} (1 <= T <= 8)")
+    perm = torch.empty(B, dtype=torch.int32, device=dev)
+    seg = torch.empty(T + 2, dtype=torch.int32, device=dev)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    status = _err_flag(dev, check)
+    _lib.run("gnn_gatne_order", types=types.data_ptr(), B=B, T=T, perm=perm.data_ptr(),
+             seg=seg.data_ptr(), status=status.data_ptr(), workspace=ws.data_ptr(),
+             workspace_bytes=ws.numel(), stream=_lib.stream_handle(dev))
+    if check and int(status.item()) != 0:
+        raise IndexError(f"gatne_order: edge type outside [0, {T})")
+    return GatneOrder(perm, seg, T)
+
+
+def _gatne_operands(c, u, w1, w2, m, order):
+    _require_device(c, u, w1, w2, m, order.perm, order.seg)
+    if c.dim() != 2 or u.dim() != 3 or w1.dim() != 3 or m.dim() != 3:
+        raise ValueError("c must be [B, E], u [B, T, U], w1 [T, U, A], m [T, U, E]")
+    B, E = c.shape
+    T, U, A = w1.shape
+    if (u.shape != (B, T, U) or m.shape != (T, U, E) or w2.numel() != T * A
+            or order.perm.numel() != B or order.seg.numel() != T + 2 or order.T != T):
+        raise ValueError("the GATNE operands do not belong together")
+    for name, t in (("c", c), ("u", u), ("w1", w1), ("w2", w2), ("m", m)):
+        if t.dtype != torch.float32:
+            raise TypeError(f"{name} must be float32 (got {t.dtype})")
+    if not gatne_supported(E, U, A, T):
+        raise ValueError(f"the GATNE kernels do not take E={E}, U={U}, A={A}, T={T} "
+                         "(gatne_supported)")
+    if c.stride(1) != 1 or c.data_ptr() % 16 or (B > 1 and (c.stride(0) % 4 or c.stride(0) < E)):
+        c = c.clone(memory_format=torch.contiguous_format)
+
+    def dense(t):
+        return t if t.is_contiguous() and t.data_ptr() % 16 == 0 else \
+            t.clone(memory_format=torch.contiguous_format)
+
+    return c, dense(u), dense(w1), dense(w2), dense(m), B, T, E, U, A
+
+
+def gatne_attend_forward(c: torch.Tensor, u: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor,
+                         m: torch.Tensor, order: GatneOrder):
+    """GATNE's edge-type attention (GATNE_Pytorch/models/GATNE.py:80-95) for centre rows c
+    [B, E], neighbour sums u [B, T, U] and the rows' types given as ``order = gatne_order(types,
+    T)`` (gnn_gatne_attend_fwd_f32): with r the type of row b, ``alpha = softmax_t(tanh(u_t
+    w1[r]) . w2[r])``, ``e = c + (sum_t alpha_t u_t) m[r]``, ``out = e / max(|e|, 1e-12)``.
+    Returns (out [B, E], alpha [B, T], inv [B] = 1 / max(|e|, 1e-12)). The per-row weight
+    tensors of the reference are never formed."""
+    c, u, w1, w2, m, B, T, E, U, A = _gatne_operands(c, u, w1, w2, m, order)
+    dev = c.device
+    out = torch.empty((B, E), dtype=torch.float32, device=dev)
+    alpha = torch.empty((B, T), dtype=torch.float32, device=dev)
+    inv = torch.empty(B, dtype=torch.float32, device=dev)
+    if B:
+        _lib.run("gnn_gatne_attend_fwd_f32", c=c.data_ptr(), ldc=c.stride(0) if B > 1 else E,
+                 u=u.data_ptr(), perm=order.perm.data_ptr(), seg=order.seg.data_ptr(), B=B, T=T,
+                 E=E, U=U, A=A, w1=w1.data_ptr(), w2=w2.data_ptr(), m=m.data_ptr(),
+                 out=out.data_ptr(), ldo=E, alpha=alpha.data_ptr(), inv=inv.data_ptr(),
+                 stream=_lib.stream_handle(dev))
+    return out, alpha, inv
+
+
+def gatne_attend_backward(g: torch.Tensor, out: torch.Tensor, u: torch.Tensor,
+                          alpha: torch.Tensor, inv: torch.Tensor, w1: torch.Tensor,
+                          w2: torch.Tensor, m: torch.Tensor, order: GatneOrder,
+                          need_du: bool = True, need_params: bool = True):
+    """The adjoint of ``gatne_attend_forward`` for g = d out [B, E] and the forward's out, alpha
+    and inv (gnn_gatne_attend_bwd_f32): (dc [B, E], du [B, T, U], dw1 [T, U, A], dw2 [T, A],
+    dm [T, U, E]); ``need_du`` / ``need_params`` False leave None in their places. The tanh is
+    recomputed; a type absent from the batch gets exact zeros; sums in a fixed order, no float
+    atomics, bit-identical from run to run."""
+    _require_device(g, out, alpha, inv)
+    g, u, w1, w2, m, B, T, E, U, A = _gatne_operands(g, u, w1, w2, m, order)
+    if (out.shape != (B, E) or alpha.shape != (B, T) or inv.shape != (B,)
+            or not (out.is_contiguous() and alpha.is_contiguous() and inv.is_contiguous())):
+        raise ValueError("out, alpha and inv must be the forward's tensors")
+    dev = g.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    dc = torch.empty((B, E), **f32)
+    du = torch.empty((B, T, U), **f32) if need_du else None
+    dw1 = dw2 = dm = None
+    if need_params:
+        dw1, dw2, dm = (torch.empty(s, **f32) for s in ((T, U, A), (T, A), (T, U, E)))
+    lib = _lib.load()
+    ws = torch.empty(max(int(lib.gnn_gatne_attend_workspace_bytes(B, T, E, U, A)), 16),
+                     dtype=torch.uint8, device=dev)
+    _lib.run("gnn_gatne_attend_bwd_f32", g=g.data_ptr(), ldg=g.stride(0) if B > 1 else E,
+             out=out.data_ptr(), ldo=E, u=u.data_ptr(), alpha=alpha.data_ptr(),
+             inv=inv.data_ptr(), perm=order.perm.data_ptr(), seg=order.seg.data_ptr(), B=B, T=T,
+             E=E, U=U, A=A, w1=w1.data_ptr(), w2=w2.data_ptr(), m=m.data_ptr(),
+             dc=dc.data_ptr(), du=_lib.ptr(du), dw1=_lib.ptr(dw1), dw2=_lib.ptr(dw2),
+             dm=_lib.ptr(dm), ws=ws.data_ptr(), ws_bytes=ws.numel(),
+             stream=_lib.stream_handle(dev))
+    return dc, du, dw1, dw2, dm

@@ -1096,6 +1096,15 @@ int gnn_sage_scatter_agg_f32(const float* dbuf, int64_t ldd, const int64_t* ptr,
                              const int32_t* slot, int64_t M, int64_t k, int64_t feat,
                              int64_t n_prev, float* dx, int64_t ldx, void* workspace,
                              int64_t workspace_bytes, void* stream);
+/* gnn_sage_scatter_agg_f32 with the factor given instead of 1 / k (k >= 1):
+ *   dx[t, :F] = scale * sum_{slots (m, j) of t} dbuf[m, 0:F]   (each term scaled, then added)
+ * scale = 1: the adjoint of a SUM over the neighbours, and of a row gather (k = 1). The passes,
+ * the workspace (gnn_sage_scatter_agg_workspace_bytes) and the checks are gnn_sage_scatter_agg_f32's;
+ * scale = 1.0f / k gives its result bit for bit. */
+int gnn_sage_scatter_agg_scaled_f32(const float* dbuf, int64_t ldd, const int64_t* ptr,
+                                    const int32_t* slot, int64_t M, int64_t k, int64_t feat,
+                                    int64_t n_prev, float* dx, int64_t ldx, float scale,
+                                    void* workspace, int64_t workspace_bytes, void* stream);
 int64_t gnn_sage_scatter_agg_maxpool_workspace_bytes(int64_t M, int64_t k, int64_t feat);
 int gnn_sage_scatter_agg_maxpool_f32(const float* dbuf, int64_t ldd, const uint8_t* arg,
                                      int64_t lda, const int64_t* ptr, const int32_t* slot,
@@ -1578,6 +1587,60 @@ int gnn_han_semantic_bwd_f32(const float* g, int64_t ldg, const float* z, int64_
                              float* dw1, float* db1, float* dw2, void* ws, int64_t ws_bytes,
                              void* stream);
 int gnn_han_tanh_f32(const float* x, float* y, int64_t n, void* stream);
+
+/*
+ * GATNE (GATNE_Pytorch/models/GATNE.py GraphEncoder.forward) without the per-row weight
+ * gathers trans_weights[node_types] / trans_weights_s1[node_types] / trans_weights_s2[node_types]:
+ * the batch rows are sorted by edge type and go through the matrix cores in tiles of 16 rows of
+ * one type, the weights of that type read once per tile. Stream-ordered, no host sync.
+ *
+ *   gnn_typed_gather_sum_f32: u[(b T + t) ldu + w] = scale * sum_k table[nbr[b, t, k] ld_n +
+ *     t ld_t + w], w in [0, W): nbr int64 [B, T, K] (contiguous), W a multiple of 4, fp32 sums in
+ *     k order, 16-B loads, 64-bit offsets. ld_t = U reads node_type_embeddings [N, T, U] in place
+ *     (ld_n = T U), ld_t = 0 a feature table [N, F]. An id outside [0, n_table) is skipped and
+ *     sets *err_flag (the caller zeroes it); the kernel never reads out of range. scale: 1 for
+ *     SUM, 1 / K for MEAN. ld_n >= (T - 1) ld_t + W.
+ *   gnn_gatne_order: a stable sort of the row ids by edge type (rocPRIM radix sort over the bits
+ *     of T): perm[p] = the batch row at sorted position p (exactly numpy's stable argsort) and
+ *     seg[t] = the first position holding a type >= t for t in [0, T + 1] (seg[T + 1] = B; T + 2
+ *     entries). A type outside [0, T) sorts last (positions [seg[T], B)) and sets *status (the
+ *     caller zeroes it): the attention stage gives such rows NaN outputs and zero gradients.
+ *   gnn_gatne_supported(E, U, A, T): 1 for U, A in {16, 32, 64, 128}, E a power of two in
+ *     [16, 256], 1 <= T <= 8.
+ *   gnn_gatne_attend_fwd_f32: for row b of type r, u_t = u[(b T + t) U ..] (u contiguous
+ *     [B, T, U]), s_t = tanh(u_t W1[r]) . w2[r], alpha = softmax_t(s), v = sum_t alpha_t u_t,
+ *     e = c[b] + v M[r], out[b] = e / max(|e|_2, 1e-12). w1 [T, U, A], w2 [T, A], m [T, U, E]
+ *     contiguous. Saves alpha [B, T] and inv[b] = 1 / max(|e|_2, 1e-12). Products on
+ *     v_mfma_f32_16x16x4_f32 (fp32), tanh as gnn_han_tanh_f32. Grid: ceil(B / 16) + T + 1
+ *     tiles, the surplus exits.
+ *   gnn_gatne_attend_bwd_f32: given g = d out [B, E]: dc [B, E], du [B, T, U] (contiguous) and,
+ *     unless dw1 is NULL, dw1 [T, U, A], dw2 [T, A], dm [T, U, E]; a type absent from the batch
+ *     gets exact zeros. inv[b] = 1e12 (|e| below eps) takes F.normalize's clamped branch
+ *     de = g / eps. The weight gradients are sums over the sorted rows of a type cut into
+ *     kGatneSplits row ranges: one partial per (type, range), added in range order. No float
+ *     atomics: bit-identical from run to run. ws: gnn_gatne_attend_workspace_bytes, 16-B aligned.
+ * Validation: negative sizes, null operands, short pitches, a short workspace -> GNN_E_ARG;
+ * misaligned rows -> GNN_E_ALIGN; widths outside gnn_gatne_supported, B > 2^31 / (16 T) ->
+ * GNN_E_UNSUPPORTED. B = 0 returns GNN_OK (the weight gradients zeroed).
+ */
+int gnn_typed_gather_sum_f32(const float* table, int64_t ld_n, int64_t ld_t, int64_t n_table,
+                             const int64_t* nbr, int64_t B, int64_t T, int64_t K, int64_t W,
+                             float scale, float* u, int64_t ldu, int32_t* err_flag, void* stream);
+int64_t gnn_gatne_order_workspace_bytes(int64_t B, int64_t T);
+int gnn_gatne_order(const int64_t* types, int64_t B, int64_t T, int32_t* perm, int32_t* seg,
+                    int32_t* status, void* workspace, int64_t workspace_bytes, void* stream);
+int gnn_gatne_supported(int64_t E, int64_t U, int64_t A, int64_t T);
+int64_t gnn_gatne_attend_workspace_bytes(int64_t B, int64_t T, int64_t E, int64_t U, int64_t A);
+int gnn_gatne_attend_fwd_f32(const float* c, int64_t ldc, const float* u, const int32_t* perm,
+                             const int32_t* seg, int64_t B, int64_t T, int64_t E, int64_t U,
+                             int64_t A, const float* w1, const float* w2, const float* m,
+                             float* out, int64_t ldo, float* alpha, float* inv, void* stream);
+int gnn_gatne_attend_bwd_f32(const float* g, int64_t ldg, const float* out, int64_t ldo,
+                             const float* u, const float* alpha, const float* inv,
+                             const int32_t* perm, const int32_t* seg, int64_t B, int64_t T,
+                             int64_t E, int64_t U, int64_t A, const float* w1, const float* w2,
+                             const float* m, float* dc, float* du, float* dw1, float* dw2,
+                             float* dm, void* ws, int64_t ws_bytes, void* stream);
 
 /*
  * Edge-cut halo exchange (SURVEY 8(b) gnn_halo_alltoallv; the all-to-all-v that
