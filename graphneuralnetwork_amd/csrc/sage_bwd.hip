@@ -50,16 +50,13 @@ constexpr int kSbChunk = GNN_SB_CHUNK;
 constexpr int kSbU = GNN_SB_U;
 constexpr int kSbGrid = 2048;  // the chunk / combine passes: a fixed grid, sizes read on the device
 
-// M (k + 1), or -1 where it does not fit an int32 slot id
+// The slots of a layer, or -1 where they do not fit an int32 slot id. CENTRE: M (k + 1); off
+// (the gcn-mode layer has no centre half): M k, slot e is entry (e / k, e % k)
+template <bool CENTRE>
 static int64_t sb_slots(int64_t M, int64_t k) {
-  if (M > 0x7fffffffLL / (k + 1)) return -1;
-  return M * (k + 1);
-}
-
-// the gcn-mode layer has no centre half: M k slots, slot e is entry (e / k, e % k)
-static int64_t sb_slots_nbr(int64_t M, int64_t k) {
-  if (k > 0 && M > 0x7fffffffLL / k) return -1;
-  return M * k;
+  const int64_t per_row = CENTRE ? k + 1 : k;
+  if (per_row > 0 && M > 0x7fffffffLL / per_row) return -1;
+  return M * per_row;
 }
 
 static unsigned sb_key_bits(int64_t n_prev) {  // keys are targets in [0, n_prev]
@@ -429,7 +426,7 @@ static int sb_transpose(const int64_t* cidx, const int64_t* idx, int64_t ldi, in
 
 extern "C" int64_t gnn_sage_maps_transpose_workspace_bytes(int64_t M, int64_t k) {
   if (M < 0 || k < 0) return GNN_E_ARG;
-  const int64_t n = sb_slots(M, k);
+  const int64_t n = sb_slots<true>(M, k);
   if (n < 0) return GNN_E_UNSUPPORTED;
   return sb_transpose_carve(nullptr, n).bytes;
 }
@@ -440,7 +437,7 @@ extern "C" int gnn_sage_maps_transpose(const int64_t* cidx, const int64_t* idx, 
                                        int64_t workspace_bytes, void* stream) {
   if (M < 0 || k < 0 || n_prev < 0 || !ptr || !err_flag || !workspace) return GNN_E_ARG;
   if (M > 0 && (!cidx || !slot || (k > 0 && (!idx || ldi < k)))) return GNN_E_ARG;
-  const int64_t n = sb_slots(M, k);
+  const int64_t n = sb_slots<true>(M, k);
   if (n < 0 || n_prev >= 0x7fffffffLL) return GNN_E_UNSUPPORTED;
   return sb_transpose<true>(cidx, idx, ldi, M, k, n_prev, n, ptr, slot, err_flag, workspace,
                             workspace_bytes, stream);
@@ -449,7 +446,7 @@ extern "C" int gnn_sage_maps_transpose(const int64_t* cidx, const int64_t* idx, 
 // the neighbour map alone (the gcn-mode layer): M k slots, slot e = entry (e / k, e % k)
 extern "C" int64_t gnn_sage_maps_transpose_nbr_workspace_bytes(int64_t M, int64_t k) {
   if (M < 0 || k < 0) return GNN_E_ARG;
-  const int64_t n = sb_slots_nbr(M, k);
+  const int64_t n = sb_slots<false>(M, k);
   if (n < 0) return GNN_E_UNSUPPORTED;
   return sb_transpose_carve(nullptr, n).bytes;
 }
@@ -460,7 +457,7 @@ extern "C" int gnn_sage_maps_transpose_nbr(const int64_t* idx, int64_t ldi, int6
                                            int64_t workspace_bytes, void* stream) {
   if (M < 0 || k < 0 || n_prev < 0 || !ptr || !err_flag || !workspace) return GNN_E_ARG;
   if (M > 0 && k > 0 && (!idx || !slot || ldi < k)) return GNN_E_ARG;
-  const int64_t n = sb_slots_nbr(M, k);
+  const int64_t n = sb_slots<false>(M, k);
   if (n < 0 || n_prev >= 0x7fffffffLL) return GNN_E_UNSUPPORTED;
   return sb_transpose<false>(nullptr, idx, ldi, M, k, n_prev, n, ptr, slot, err_flag, workspace,
                              workspace_bytes, stream);
@@ -469,13 +466,6 @@ extern "C" int gnn_sage_maps_transpose_nbr(const int64_t* idx, int64_t ldi, int6
 extern "C" int gnn_sage_scatter_concat_supported(int64_t feat) {
   // F / 4 lanes per row, a power of two of them per wavefront
   return feat >= 4 && feat <= 256 && (feat & (feat - 1)) == 0;
-}
-
-extern "C" int64_t gnn_sage_scatter_concat_workspace_bytes(int64_t M, int64_t k, int64_t feat) {
-  if (M < 0 || k < 0 || feat < 0) return GNN_E_ARG;
-  const int64_t n = sb_slots(M, k);
-  if (n < 0 || !gnn_sage_scatter_concat_supported(feat)) return GNN_E_UNSUPPORTED;
-  return sb_carve(nullptr, n, feat).bytes;
 }
 
 template <typename A>
@@ -491,11 +481,67 @@ static int dispatch_sage_scatter(const A& a, int64_t feat, hipStream_t s) {
   }
 }
 
+// The body of the four workspace queries. CENTRE: the concat layer (dbuf [M, 2F], the maps of
+// gnn_sage_maps_transpose); off: the gcn-mode layer (dbuf [M, F], gnn_sage_maps_transpose_nbr).
+// MASK: the MAXPOOL select, whose uint8 winner holds k in [1, 255]; the layout is the MEAN one.
+template <bool CENTRE, bool MASK>
+static int64_t sb_scatter_bytes(int64_t M, int64_t k, int64_t feat) {
+  if (M < 0 || k < 0 || feat < 0) return GNN_E_ARG;
+  if (MASK && (k < 1 || k > 255)) return GNN_E_UNSUPPORTED;
+  const int64_t n = sb_slots<CENTRE>(M, k);
+  if (n < 0 || !gnn_sage_scatter_concat_supported(feat)) return GNN_E_UNSUPPORTED;
+  return sb_carve(nullptr, n, feat).bytes;
+}
+
+// The body of the five scatter entries (CENTRE, MASK as above; arg / lda are read with MASK
+// only). `scale` multiplies every neighbour slot's row of a MEAN form; the select never scales.
+template <bool CENTRE, bool MASK>
+static int sb_scatter(const float* dbuf, int64_t ldd, const uint8_t* arg, int64_t lda,
+                      const int64_t* ptr, const int32_t* slot, int64_t M, int64_t k, int64_t feat,
+                      int64_t n_prev, float* dx, int64_t ldx, float scale, void* workspace,
+                      int64_t workspace_bytes, void* stream) {
+  if (M < 0 || k < 0 || feat < 0 || n_prev < 0) return GNN_E_ARG;
+  if (!ptr || !workspace || (n_prev > 0 && !dx) || (M > 0 && (!dbuf || !slot || (MASK && !arg))))
+    return GNN_E_ARG;
+  const int64_t n = sb_slots<CENTRE>(M, k);
+  if (n < 0 || n_prev >= 0x7fffffffLL || !gnn_sage_scatter_concat_supported(feat) ||
+      (MASK && (k < 1 || k > 255)))
+    return GNN_E_UNSUPPORTED;
+  if (ldd < (CENTRE ? 2 * feat : feat) || ldx < feat || (MASK && lda < feat)) return GNN_E_ARG;
+  const SbWs w = sb_carve(workspace, n, feat);
+  if (workspace_bytes < w.bytes) return GNN_E_ARG;
+  if (ldd % 4 || ldx % 4 || !aligned_to(dbuf, 16) || !aligned_to(dx, 16) ||
+      (MASK && (lda % 4 || !aligned_to(arg, 4))) || !aligned_to(workspace, 16))
+    return GNN_E_ALIGN;
+  if (n_prev == 0) return GNN_OK;
+  const SbArgs mean{dbuf, ldd, ptr, slot, M, k, n_prev, n, scale, dx, ldx, w.count, w.longs,
+                    w.tasks, w.part, w.max_long, w.max_tasks};
+  const SbMaskArgs mask{mean, arg, lda};
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if constexpr (CENTRE && MASK) return dispatch_sage_scatter(mask, feat, s);
+  else if constexpr (CENTRE) return dispatch_sage_scatter(mean, feat, s);
+  else if constexpr (MASK) return dispatch_sage_scatter(SbAggMaskArgs{mask}, feat, s);
+  else return dispatch_sage_scatter(SbAggArgs{mean}, feat, s);
+}
+
+static float sb_inv(int64_t k) { return k > 0 ? 1.0f / static_cast<float>(k) : 0.f; }
+
+extern "C" int64_t gnn_sage_scatter_concat_workspace_bytes(int64_t M, int64_t k, int64_t feat) {
+  return sb_scatter_bytes<true, false>(M, k, feat);
+}
+
 extern "C" int64_t gnn_sage_scatter_concat_maxpool_workspace_bytes(int64_t M, int64_t k,
                                                                    int64_t feat) {
-  if (M < 0 || k < 0 || feat < 0) return GNN_E_ARG;
-  if (k < 1 || k > 255) return GNN_E_UNSUPPORTED;
-  return gnn_sage_scatter_concat_workspace_bytes(M, k, feat);  // the MEAN scatter's layout
+  return sb_scatter_bytes<true, true>(M, k, feat);
+}
+
+extern "C" int64_t gnn_sage_scatter_agg_workspace_bytes(int64_t M, int64_t k, int64_t feat) {
+  return sb_scatter_bytes<false, false>(M, k, feat);
+}
+
+extern "C" int64_t gnn_sage_scatter_agg_maxpool_workspace_bytes(int64_t M, int64_t k,
+                                                                int64_t feat) {
+  return sb_scatter_bytes<false, true>(M, k, feat);
 }
 
 extern "C" int gnn_sage_scatter_concat_maxpool_f32(const float* dbuf, int64_t ldd,
@@ -505,91 +551,24 @@ extern "C" int gnn_sage_scatter_concat_maxpool_f32(const float* dbuf, int64_t ld
                                                    int64_t n_prev, float* dx, int64_t ldx,
                                                    void* workspace, int64_t workspace_bytes,
                                                    void* stream) {
-  if (M < 0 || k < 0 || feat < 0 || n_prev < 0) return GNN_E_ARG;
-  if (!ptr || !workspace || (n_prev > 0 && !dx) || (M > 0 && (!dbuf || !slot || !arg)))
-    return GNN_E_ARG;
-  const int64_t n = sb_slots(M, k);
-  if (n < 0 || n_prev >= 0x7fffffffLL || !gnn_sage_scatter_concat_supported(feat) || k < 1 ||
-      k > 255)
-    return GNN_E_UNSUPPORTED;
-  if (ldd < 2 * feat || ldx < feat || lda < feat) return GNN_E_ARG;
-  const SbWs w = sb_carve(workspace, n, feat);
-  if (workspace_bytes < w.bytes) return GNN_E_ARG;
-  if (ldd % 4 || ldx % 4 || lda % 4 || !aligned_to(dbuf, 16) || !aligned_to(dx, 16) ||
-      !aligned_to(arg, 4) || !aligned_to(workspace, 16))
-    return GNN_E_ALIGN;
-  if (n_prev == 0) return GNN_OK;
-  SbMaskArgs a{{dbuf, ldd, ptr, slot, M, k, n_prev, n, 1.f, dx, ldx, w.count, w.longs, w.tasks,
-                w.part, w.max_long, w.max_tasks},
-               arg, lda};
-  return dispatch_sage_scatter(a, feat, static_cast<hipStream_t>(stream));
+  return sb_scatter<true, true>(dbuf, ldd, arg, lda, ptr, slot, M, k, feat, n_prev, dx, ldx, 1.f,
+                                workspace, workspace_bytes, stream);
 }
 
 extern "C" int gnn_sage_scatter_concat_f32(const float* dbuf, int64_t ldd, const int64_t* ptr,
                                            const int32_t* slot, int64_t M, int64_t k, int64_t feat,
                                            int64_t n_prev, float* dx, int64_t ldx, void* workspace,
                                            int64_t workspace_bytes, void* stream) {
-  if (M < 0 || k < 0 || feat < 0 || n_prev < 0) return GNN_E_ARG;
-  if (!ptr || !workspace || (n_prev > 0 && !dx) || (M > 0 && (!dbuf || !slot))) return GNN_E_ARG;
-  const int64_t n = sb_slots(M, k);
-  if (n < 0 || n_prev >= 0x7fffffffLL || !gnn_sage_scatter_concat_supported(feat))
-    return GNN_E_UNSUPPORTED;
-  if (ldd < 2 * feat || ldx < feat) return GNN_E_ARG;
-  const SbWs w = sb_carve(workspace, n, feat);
-  if (workspace_bytes < w.bytes) return GNN_E_ARG;
-  if (ldd % 4 || ldx % 4 || !aligned_to(dbuf, 16) || !aligned_to(dx, 16) ||
-      !aligned_to(workspace, 16))
-    return GNN_E_ALIGN;
-  if (n_prev == 0) return GNN_OK;
-  SbArgs a{dbuf, ldd, ptr, slot, M, k, n_prev, n, k > 0 ? 1.0f / static_cast<float>(k) : 0.f, dx,
-           ldx, w.count, w.longs, w.tasks, w.part, w.max_long, w.max_tasks};
-  return dispatch_sage_scatter(a, feat, static_cast<hipStream_t>(stream));
-}
-
-// ---- the gcn-mode layer: dbuf is [M, F] (no centre half), the maps gnn_sage_maps_transpose_nbr's
-extern "C" int64_t gnn_sage_scatter_agg_workspace_bytes(int64_t M, int64_t k, int64_t feat) {
-  if (M < 0 || k < 0 || feat < 0) return GNN_E_ARG;
-  const int64_t n = sb_slots_nbr(M, k);
-  if (n < 0 || !gnn_sage_scatter_concat_supported(feat)) return GNN_E_UNSUPPORTED;
-  return sb_carve(nullptr, n, feat).bytes;
-}
-
-extern "C" int64_t gnn_sage_scatter_agg_maxpool_workspace_bytes(int64_t M, int64_t k,
-                                                                int64_t feat) {
-  if (M < 0 || k < 0 || feat < 0) return GNN_E_ARG;
-  if (k < 1 || k > 255) return GNN_E_UNSUPPORTED;
-  return gnn_sage_scatter_agg_workspace_bytes(M, k, feat);  // the MEAN scatter's layout
-}
-
-// the body of gnn_sage_scatter_agg_f32 and its scaled twin: `scale` multiplies every slot's row
-static int sb_scatter_agg(const float* dbuf, int64_t ldd, const int64_t* ptr, const int32_t* slot,
-                          int64_t M, int64_t k, int64_t feat, int64_t n_prev, float* dx,
-                          int64_t ldx, float scale, void* workspace, int64_t workspace_bytes,
-                          void* stream) {
-  if (M < 0 || k < 0 || feat < 0 || n_prev < 0) return GNN_E_ARG;
-  if (!ptr || !workspace || (n_prev > 0 && !dx) || (M > 0 && (!dbuf || !slot))) return GNN_E_ARG;
-  const int64_t n = sb_slots_nbr(M, k);
-  if (n < 0 || n_prev >= 0x7fffffffLL || !gnn_sage_scatter_concat_supported(feat))
-    return GNN_E_UNSUPPORTED;
-  if (ldd < feat || ldx < feat) return GNN_E_ARG;
-  const SbWs w = sb_carve(workspace, n, feat);
-  if (workspace_bytes < w.bytes) return GNN_E_ARG;
-  if (ldd % 4 || ldx % 4 || !aligned_to(dbuf, 16) || !aligned_to(dx, 16) ||
-      !aligned_to(workspace, 16))
-    return GNN_E_ALIGN;
-  if (n_prev == 0) return GNN_OK;
-  SbAggArgs a{{dbuf, ldd, ptr, slot, M, k, n_prev, n, scale, dx, ldx, w.count, w.longs, w.tasks,
-               w.part, w.max_long, w.max_tasks}};
-  return dispatch_sage_scatter(a, feat, static_cast<hipStream_t>(stream));
+  return sb_scatter<true, false>(dbuf, ldd, nullptr, 0, ptr, slot, M, k, feat, n_prev, dx, ldx,
+                                 sb_inv(k), workspace, workspace_bytes, stream);
 }
 
 extern "C" int gnn_sage_scatter_agg_f32(const float* dbuf, int64_t ldd, const int64_t* ptr,
                                         const int32_t* slot, int64_t M, int64_t k, int64_t feat,
                                         int64_t n_prev, float* dx, int64_t ldx, void* workspace,
                                         int64_t workspace_bytes, void* stream) {
-  return sb_scatter_agg(dbuf, ldd, ptr, slot, M, k, feat, n_prev, dx, ldx,
-                        k > 0 ? 1.0f / static_cast<float>(k) : 0.f, workspace, workspace_bytes,
-                        stream);
+  return sb_scatter<false, false>(dbuf, ldd, nullptr, 0, ptr, slot, M, k, feat, n_prev, dx, ldx,
+                                  sb_inv(k), workspace, workspace_bytes, stream);
 }
 
 // the factor given by the caller (1 for a SUM over the neighbours or a row gather, k = 1)
@@ -599,8 +578,8 @@ extern "C" int gnn_sage_scatter_agg_scaled_f32(const float* dbuf, int64_t ldd, c
                                                int64_t ldx, float scale, void* workspace,
                                                int64_t workspace_bytes, void* stream) {
   if (k < 1) return k < 0 ? GNN_E_ARG : GNN_E_UNSUPPORTED;
-  return sb_scatter_agg(dbuf, ldd, ptr, slot, M, k, feat, n_prev, dx, ldx, scale, workspace,
-                        workspace_bytes, stream);
+  return sb_scatter<false, false>(dbuf, ldd, nullptr, 0, ptr, slot, M, k, feat, n_prev, dx, ldx,
+                                  scale, workspace, workspace_bytes, stream);
 }
 
 extern "C" int gnn_sage_scatter_agg_maxpool_f32(const float* dbuf, int64_t ldd, const uint8_t* arg,
@@ -609,22 +588,6 @@ extern "C" int gnn_sage_scatter_agg_maxpool_f32(const float* dbuf, int64_t ldd, 
                                                 int64_t feat, int64_t n_prev, float* dx,
                                                 int64_t ldx, void* workspace,
                                                 int64_t workspace_bytes, void* stream) {
-  if (M < 0 || k < 0 || feat < 0 || n_prev < 0) return GNN_E_ARG;
-  if (!ptr || !workspace || (n_prev > 0 && !dx) || (M > 0 && (!dbuf || !slot || !arg)))
-    return GNN_E_ARG;
-  const int64_t n = sb_slots_nbr(M, k);
-  if (n < 0 || n_prev >= 0x7fffffffLL || !gnn_sage_scatter_concat_supported(feat) || k < 1 ||
-      k > 255)
-    return GNN_E_UNSUPPORTED;
-  if (ldd < feat || ldx < feat || lda < feat) return GNN_E_ARG;
-  const SbWs w = sb_carve(workspace, n, feat);
-  if (workspace_bytes < w.bytes) return GNN_E_ARG;
-  if (ldd % 4 || ldx % 4 || lda % 4 || !aligned_to(dbuf, 16) || !aligned_to(dx, 16) ||
-      !aligned_to(arg, 4) || !aligned_to(workspace, 16))
-    return GNN_E_ALIGN;
-  if (n_prev == 0) return GNN_OK;
-  SbAggMaskArgs a{{{dbuf, ldd, ptr, slot, M, k, n_prev, n, 1.f, dx, ldx,
-                    w.count, w.longs, w.tasks, w.part, w.max_long, w.max_tasks},
-                   arg, lda}};
-  return dispatch_sage_scatter(a, feat, static_cast<hipStream_t>(stream));
+  return sb_scatter<false, true>(dbuf, ldd, arg, lda, ptr, slot, M, k, feat, n_prev, dx, ldx, 1.f,
+                                 workspace, workspace_bytes, stream);
 }

@@ -274,7 +274,7 @@ class GraphDecoder(nn.Module):
                 and contest_negative.dim() == 2 and contest_negative.shape[0] == embed.shape[0]
                 and embed.shape[0] > 0 and contest_negative.shape[1] > 0
                 and embed.shape[1] == self.embedding_size
-                and bool(ops._lib.load().gnn_sage_scatter_concat_supported(self.embedding_size)))
+                and ops.sage_scatter_supported(self.embedding_size))
 
     def forward(self, embed, contest_negative):
         if self._fused_ok(embed, contest_negative):

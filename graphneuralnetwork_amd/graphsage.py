@@ -401,6 +401,26 @@ def _fused_gcn_layer(block, neigh: Gathered, dense: nn.Linear | None = None, agg
 SAGE_TRAIN_FUSED = True
 
 
+def _train_layer_backward(ctx, dy, buf, y, W, scatter):
+    """The backward of the three training-layer functions, with dY' = dY . [y > 0]:
+    dW = dY'^T buf in one masked pass (``gemm_tn_masked``; torch's mm where it declines) and,
+    only for a table that requires grad, d table = ``scatter(dBuf)`` with dBuf = dY' W -- the
+    adjoint of the layer's own gather, which each function supplies."""
+    d_table = dW = g = None
+    if ctx.needs_input_grad[1]:
+        r = gemm_tn_masked(buf, dy, y, 1.0, False, trans=True)
+        if r is not None:
+            dW = r[0]
+        else:
+            g = _masked_grad(dy, y, 1.0)
+            dW = torch.mm(g.t(), buf)
+    if ctx.needs_input_grad[0]:
+        if g is None:
+            g = _masked_grad(dy, y, 1.0)
+        d_table = scatter(_transform_or_mm(g, W.t().contiguous()))
+    return d_table, dW, None, None
+
+
 class _SageTrainLayerFn(torch.autograd.Function):
     """relu(W . cat[table[cidx], mean_j table[idx[:, j]]]) (GraphSAGE/GraphSAGE.py:17-20 over
     the gathers of :47-49) with autograd w.r.t. W and, where it asks for it, the fp32 table.
@@ -426,26 +446,17 @@ class _SageTrainLayerFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         buf, y, W, cidx, idx = ctx.saved_tensors
-        d_table = dW = g = None
-        if ctx.needs_input_grad[1]:
-            r = gemm_tn_masked(buf, dy, y, 1.0, False, trans=True)
-            if r is not None:
-                dW = r[0]
-            else:
-                g = _masked_grad(dy, y, 1.0)
-                dW = torch.mm(g.t(), buf)
-        if ctx.needs_input_grad[0]:
-            if g is None:
-                g = _masked_grad(dy, y, 1.0)
-            dbuf = _transform_or_mm(g, W.t().contiguous())
+
+        def scatter(dbuf):
             tr = sage_maps_transpose(cidx, idx, ctx.n_prev, check=False)
-            if tr is not None:
-                d_table = sage_scatter_concat(dbuf, tr, ctx.n_prev)
-            if d_table is None:  # a shape the kernel declines: the SpMM over a Python-built CSR
+            d = None if tr is None else sage_scatter_concat(dbuf, tr, ctx.n_prev)
+            if d is None:  # a shape the kernel declines: the SpMM over a Python-built CSR
                 n = W.shape[1] // 2
-                d_table = (_scatter_rows(dbuf[:, :n], cidx.reshape(-1, 1), ctx.n_prev, 1.0)
-                           + _scatter_rows(dbuf[:, n:], idx, ctx.n_prev, 1.0 / idx.shape[1]))
-        return d_table, dW, None, None
+                d = (_scatter_rows(dbuf[:, :n], cidx.reshape(-1, 1), ctx.n_prev, 1.0)
+                     + _scatter_rows(dbuf[:, n:], idx, ctx.n_prev, 1.0 / idx.shape[1]))
+            return d
+
+        return _train_layer_backward(ctx, dy, buf, y, W, scatter)
 
 
 # The same for agg_func 'MAXPOOL' (``_SageMaxPoolTrainLayerFn``). False: the separate row gather,
@@ -457,13 +468,22 @@ SAGE_TRAIN_FUSED_MAXPOOL = True
 def _maxpool_scatter_torch(dbuf, arg, cidx, idx, n_prev):
     """The masked sum of ``sage_scatter_concat_maxpool`` in torch, for a shape it declines:
     the centre rows by index_add_, each (row, feature) of the aggregate half onto the table row
-    of its winner by index_put_ (float atomics: the order of the sums is not fixed)."""
-    n = dbuf.shape[1] // 2
+    of its winner by index_put_ (float atomics: the order of the sums is not fixed).
+    ``cidx`` None: ``sage_scatter_agg_maxpool``'s (the gcn-mode layer), dbuf [M, F] with no
+    centre half."""
+    n = dbuf.shape[1] if cidx is None else dbuf.shape[1] // 2
     out = torch.zeros((n_prev, n), dtype=dbuf.dtype, device=dbuf.device)
-    out.index_add_(0, cidx, dbuf[:, :n])
+    if cidx is not None:
+        out.index_add_(0, cidx, dbuf[:, :n])
+        dbuf = dbuf[:, n:]
     rows = idx.gather(1, arg.to(torch.int64))                     # [M, F] table rows
     cols = torch.arange(n, device=dbuf.device).expand_as(rows)
-    return out.index_put_((rows, cols), dbuf[:, n:], accumulate=True)
+    return out.index_put_((rows, cols), dbuf, accumulate=True)
+
+
+def _gcn_maxpool_scatter_torch(dbuf, arg, idx, n_prev):
+    """``_maxpool_scatter_torch`` without the centre half (tools/sage_train_ab.py times it)."""
+    return _maxpool_scatter_torch(dbuf, arg, None, idx, n_prev)
 
 
 class _SageMaxPoolTrainLayerFn(torch.autograd.Function):
@@ -495,33 +515,15 @@ class _SageMaxPoolTrainLayerFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         buf, y, W, cidx, idx, arg = ctx.saved_tensors
-        d_table = dW = g = None
-        if ctx.needs_input_grad[1]:
-            r = gemm_tn_masked(buf, dy, y, 1.0, False, trans=True)
-            if r is not None:
-                dW = r[0]
-            else:
-                g = _masked_grad(dy, y, 1.0)
-                dW = torch.mm(g.t(), buf)
-        if ctx.needs_input_grad[0]:
-            if g is None:
-                g = _masked_grad(dy, y, 1.0)
-            dbuf = _transform_or_mm(g, W.t().contiguous())
+
+        def scatter(dbuf):
             tr = sage_maps_transpose(cidx, idx, ctx.n_prev, check=False)
-            if tr is not None:
-                d_table = sage_scatter_concat_maxpool(dbuf, arg, tr, ctx.n_prev)
-            if d_table is None:  # a shape the kernel declines
-                d_table = _maxpool_scatter_torch(dbuf, arg, cidx, idx, ctx.n_prev)
-        return d_table, dW, None, None
+            d = None if tr is None else sage_scatter_concat_maxpool(dbuf, arg, tr, ctx.n_prev)
+            if d is None:  # a shape the kernel declines
+                d = _maxpool_scatter_torch(dbuf, arg, cidx, idx, ctx.n_prev)
+            return d
 
-
-def _gcn_maxpool_scatter_torch(dbuf, arg, idx, n_prev):
-    """The masked sum of ``sage_scatter_agg_maxpool`` in torch, for a shape it declines: each
-    (row, feature) onto the table row of its winner by index_put_ (float atomics)."""
-    out = torch.zeros((n_prev, dbuf.shape[1]), dtype=dbuf.dtype, device=dbuf.device)
-    rows = idx.gather(1, arg.to(torch.int64))                     # [M, F] table rows
-    cols = torch.arange(dbuf.shape[1], device=dbuf.device).expand_as(rows)
-    return out.index_put_((rows, cols), dbuf, accumulate=True)
+        return _train_layer_backward(ctx, dy, buf, y, W, scatter)
 
 
 class _SageGcnTrainLayerFn(torch.autograd.Function):
@@ -556,37 +558,35 @@ class _SageGcnTrainLayerFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         buf, y, W, idx, arg = ctx.saved_tensors
-        d_table = dW = g = None
-        if ctx.needs_input_grad[1]:
-            r = gemm_tn_masked(buf, dy, y, 1.0, False, trans=True)
-            if r is not None:
-                dW = r[0]
-            else:
-                g = _masked_grad(dy, y, 1.0)
-                dW = torch.mm(g.t(), buf)
-        if ctx.needs_input_grad[0]:
-            if g is None:
-                g = _masked_grad(dy, y, 1.0)
-            dbuf = _transform_or_mm(g, W.t().contiguous())
+
+        def scatter(dbuf):
             tr = sage_maps_transpose_nbr(idx, ctx.n_prev, check=False)
+            d = None
             if tr is not None:
-                d_table = (sage_scatter_agg(dbuf, tr, ctx.n_prev) if arg is None else
-                           sage_scatter_agg_maxpool(dbuf, arg, tr, ctx.n_prev))
-            if d_table is None:  # a shape the kernel declines
-                d_table = (_scatter_rows(dbuf, idx, ctx.n_prev, 1.0 / idx.shape[1])
-                           if arg is None else
-                           _gcn_maxpool_scatter_torch(dbuf, arg, idx, ctx.n_prev))
-        return d_table, dW, None, None
+                d = (sage_scatter_agg(dbuf, tr, ctx.n_prev) if arg is None else
+                     sage_scatter_agg_maxpool(dbuf, arg, tr, ctx.n_prev))
+            if d is None:  # a shape the kernel declines
+                d = (_scatter_rows(dbuf, idx, ctx.n_prev, 1.0 / idx.shape[1]) if arg is None else
+                     _maxpool_scatter_torch(dbuf, arg, None, idx, ctx.n_prev))
+            return d
+
+        return _train_layer_backward(ctx, dy, buf, y, W, scatter)
+
+
+def _train_layer_takes(table, W, idx, agg: str, gcn: bool) -> bool:
+    """What both training layers ask of a batch before ``sage_train_layer_supported``: an int64
+    [M, k] map with rows, somebody who wants a gradient, and no bfloat16 table among them."""
+    return (idx.dim() == 2 and idx.dtype == torch.int64 and idx.shape[0] > 0
+            and (W.requires_grad or table.requires_grad)
+            and not (table.dtype == torch.bfloat16 and table.requires_grad)  # raises as before
+            and sage_train_layer_supported(table, W, idx.shape[1], agg, gcn=gcn))
 
 
 def _sage_gcn_train_layer(block, neigh: Gathered, agg: str):
     """The gcn-mode training SageLayer on a trusted map, or None where ``_SageGcnTrainLayerFn``
     does not cover the layer (the caller takes the unfused path)."""
     table, W, idx = neigh.table, block.weight.weight, neigh.index
-    if (idx.dim() != 2 or idx.dtype != torch.int64 or idx.shape[0] == 0
-            or not (W.requires_grad or table.requires_grad)
-            or (table.dtype == torch.bfloat16 and table.requires_grad)  # raises as before
-            or not sage_train_layer_supported(table, W, idx.shape[1], agg, gcn=True)):
+    if not _train_layer_takes(table, W, idx, agg, True):
         return None
     return _SageGcnTrainLayerFn.apply(table, W, idx, agg)
 
@@ -597,11 +597,8 @@ def _sage_train_layer(block, center: Gathered, neigh: Gathered, agg: str = 'MEAN
     takes the unfused path)."""
     table, W = neigh.table, block.weight.weight
     idx, cidx = neigh.index, center.index
-    if (idx.dim() != 2 or idx.dtype != torch.int64 or cidx.dtype != torch.int64
-            or cidx.numel() != idx.shape[0] or idx.shape[0] == 0
-            or not (W.requires_grad or table.requires_grad)
-            or (table.dtype == torch.bfloat16 and table.requires_grad)  # raises as before
-            or not sage_train_layer_supported(table, W, idx.shape[1], agg)):
+    if (idx.dim() != 2 or cidx.dtype != torch.int64 or cidx.numel() != idx.shape[0]
+            or not _train_layer_takes(table, W, idx, agg, False)):
         return None
     fn = _SageMaxPoolTrainLayerFn if agg == 'MAXPOOL' else _SageTrainLayerFn
     return fn.apply(table, W, cidx, idx)

@@ -1523,9 +1523,9 @@ def gat_aggregate(g: CsrGraph, wh: torch.Tensor, el: torch.Tensor, er: torch.Ten
 
 
 # ---------------------------------------------------------------- GraphSAGE
-SAGE_MODES = {"MEAN": 0, "MAX": 1}   # GraphSAGE/graph_utils.py Aggregator
-# + NeighborAggregator 'sum' (GraphSAGE_Pytorch) and the value max-pool the north star names
-# ("mean/max-pool"; torch.max(dim=1).values, GraphSAGE_Pytorch/models/Aggregator.py:23-24)
+# 'MEAN' / 'MAX' of GraphSAGE/graph_utils.py's Aggregator + NeighborAggregator 'sum'
+# (GraphSAGE_Pytorch) and the value max-pool the north star names ("mean/max-pool";
+# torch.max(dim=1).values, GraphSAGE_Pytorch/models/Aggregator.py:23-24)
 SAGE_KINDS = {"MEAN": 0, "MAX": 1, "SUM": 2, "MAXPOOL": 3}
 
 
@@ -1564,9 +1564,7 @@ def sage_aggregate(neigh: torch.Tensor, agg_func: str = "MEAN") -> torch.Tensor:
         _empty_reduction(mode)
         return torch.full((M, F), _EMPTY_FILL[mode], device=neigh.device)
     out = _sage_out(M, F, mode, neigh.device)
-    lib = _lib.load()
-    fn, name = ((lib.gnn_sage_aggregate_bf16, "gnn_sage_aggregate_bf16") if _bf16(neigh) else
-                (lib.gnn_sage_aggregate_f32, "gnn_sage_aggregate_f32"))
+    fn, name = _twin(_lib.load(), "gnn_sage_aggregate", neigh)
     _lib.check(fn(neigh.data_ptr(), neigh.stride(1), neigh.stride(0), M, k, F, mode,
                   out.data_ptr(), F, _lib.stream_handle(neigh.device)), name)
     return out
@@ -1589,6 +1587,49 @@ def _err_flag(dev, check: bool) -> torch.Tensor:
 def _check_err(err: torch.Tensor, what: str) -> None:
     if int(err.item()) != 0:
         raise IndexError(f"{what}: index out of range in self")
+
+
+def _sage_table(t: torch.Tensor, name: str, what: str, *others) -> torch.Tensor:
+    """The table operand of op ``what``: float32 or bfloat16 (checked before anything else looks
+    at the tensor), on the device like ``others``, [rows, F] with unit column stride (copied
+    where it is not), and not a bfloat16 table that asks for a gradient."""
+    if t.dtype != torch.float32 and t.dtype != torch.bfloat16:
+        raise TypeError(f"{name} must be float32 or bfloat16 (got {t.dtype})")
+    _require_device(t, *others)
+    if t.dim() != 2:
+        raise ValueError(f"{name} must be 2-D [rows, features]")
+    if t.stride(1) != 1:
+        t = t.contiguous()
+    if t.dtype == torch.bfloat16:
+        _bf16_inference_only(t, what)
+    return t
+
+
+def _sage_idx(idx: torch.Tensor) -> torch.Tensor:
+    """The [M, k] neighbour index as int64 with unit column stride (any row stride)."""
+    if idx.dim() != 2:
+        raise ValueError("idx must be [M, k]")
+    idx = idx.to(torch.int64)
+    return idx if idx.stride(1) == 1 else idx.contiguous()
+
+
+def _sage_self_idx(self_idx: torch.Tensor, M: int) -> torch.Tensor:
+    """The centre index as a flat contiguous int64 tensor, one entry per output row."""
+    self_idx = self_idx.to(torch.int64).contiguous().view(-1)
+    if self_idx.numel() != M:
+        raise ValueError("self_idx must hold one index per output row")
+    return self_idx
+
+
+def _sage_live(live: torch.Tensor) -> None:
+    if live.dtype != torch.int64 or live.numel() != 1:
+        raise TypeError("live must be a one-element int64 device tensor")
+
+
+def _twin(lib, stem: str, t: torch.Tensor):
+    """(entry, its name) of the pair ``stem`` + '_f32' / '_bf16', chosen by t's dtype."""
+    name = stem + ("_bf16" if t.dtype == torch.bfloat16 else "_f32")
+    return getattr(lib, name), name
 
 
 def _sage_dst(out, M, F, mode, dev):
@@ -1615,15 +1656,8 @@ def sage_gather_aggregate(table: torch.Tensor, idx: torch.Tensor, agg_func: str 
         raise RuntimeError(f"unknown agg_func {agg_func!r}")
     if live is not None and agg_func not in ("MEAN", "MAXPOOL"):
         raise ValueError("live= is supported for 'MEAN' and 'MAXPOOL' only")
-    _f32_or_bf16(table, "table")
-    _require_device(table, idx, live)
-    table = _rows_x(table, "table")
-    _bf16_inference_only(table, "sage_gather_aggregate")
-    if idx.dim() != 2:
-        raise ValueError("idx must be [M, k]")
-    idx = idx.to(torch.int64)
-    if idx.stride(1) != 1:
-        idx = idx.contiguous()
+    table = _sage_table(table, "table", "sage_gather_aggregate", idx, live)
+    idx = _sage_idx(idx)
     M, k = idx.shape
     F = table.shape[1]
     mode = SAGE_KINDS[agg_func]
@@ -1634,25 +1668,17 @@ def sage_gather_aggregate(table: torch.Tensor, idx: torch.Tensor, agg_func: str 
     err = _err_flag(table.device, check)
     lib = _lib.load()
     if live is not None:
-        if live.dtype != torch.int64 or live.numel() != 1:
-            raise TypeError("live must be a one-element int64 device tensor")
-        fn, name = ((lib.gnn_sage_gather_aggregate_live_bf16, "gnn_sage_gather_aggregate_live_bf16")
-                    if _bf16(table) else
-                    (lib.gnn_sage_gather_aggregate_live_f32, "gnn_sage_gather_aggregate_live_f32"))
-        _lib.check(fn(
-            table.data_ptr(), table.stride(0), table.shape[0], idx.data_ptr(), idx.stride(0), M,
-            live.data_ptr(), k, F, mode, out.data_ptr(), out.stride(0), err.data_ptr(),
-            _lib.stream_handle(table.device)), name)
-        if check:
-            _check_err(err, "sage_gather_aggregate")
-        return out
-    fn, name = ((lib.gnn_sage_gather_aggregate_bf16, "gnn_sage_gather_aggregate_bf16")
-                if _bf16(table) else
-                (lib.gnn_sage_gather_aggregate_f32, "gnn_sage_gather_aggregate_f32"))
-    _lib.check(fn(
-        table.data_ptr(), table.stride(0), table.shape[0], idx.data_ptr(), idx.stride(0), M, k, F,
-        mode, out.data_ptr(), out.stride(0), err.data_ptr(), _lib.stream_handle(table.device)),
-        name)
+        _sage_live(live)
+        fn, name = _twin(lib, "gnn_sage_gather_aggregate_live", table)
+        rc = fn(table.data_ptr(), table.stride(0), table.shape[0], idx.data_ptr(), idx.stride(0),
+                M, live.data_ptr(), k, F, mode, out.data_ptr(), out.stride(0), err.data_ptr(),
+                _lib.stream_handle(table.device))
+    else:
+        fn, name = _twin(lib, "gnn_sage_gather_aggregate", table)
+        rc = fn(table.data_ptr(), table.stride(0), table.shape[0], idx.data_ptr(), idx.stride(0),
+                M, k, F, mode, out.data_ptr(), out.stride(0), err.data_ptr(),
+                _lib.stream_handle(table.device))
+    _lib.check(rc, name)
     if check:
         _check_err(err, "sage_gather_aggregate")
     return out
@@ -1674,20 +1700,11 @@ def sage_gather_concat(table: torch.Tensor, self_idx: torch.Tensor, idx: torch.T
     if agg_func not in ("MEAN", "SUM", "MAXPOOL", "MAX"):
         raise RuntimeError(f"agg_func {agg_func!r} has no concat form")
     mode = 4 if agg_func == "MAX" else SAGE_KINDS[agg_func]
-    _f32_or_bf16(table, "table")
-    _require_device(table, self_idx, idx, out)
-    table = _rows_x(table, "table")
-    _bf16_inference_only(table, "sage_gather_concat")
-    if idx.dim() != 2:
-        raise ValueError("idx must be [M, k]")
-    idx = idx.to(torch.int64)
-    if idx.stride(1) != 1:
-        idx = idx.contiguous()
-    self_idx = self_idx.to(torch.int64).contiguous().view(-1)
+    table = _sage_table(table, "table", "sage_gather_concat", self_idx, idx, out)
+    idx = _sage_idx(idx)
     M, k = idx.shape
     F = table.shape[1]
-    if self_idx.numel() != M:
-        raise ValueError("self_idx must hold one index per output row")
+    self_idx = _sage_self_idx(self_idx, M)
     if out is None:
         out = torch.empty((M, 2 * F), dtype=torch.float32, device=table.device)
     elif out.shape != (M, 2 * F) or out.dtype != torch.float32 or out.stride(1) != 1:
@@ -1701,13 +1718,9 @@ def sage_gather_concat(table: torch.Tensor, self_idx: torch.Tensor, idx: torch.T
         return out
     if live is not None:
         _require_device(live)
-        if live.dtype != torch.int64 or live.numel() != 1:
-            raise TypeError("live must be a one-element int64 device tensor")
+        _sage_live(live)
     err = _err_flag(table.device, check)
-    lib = _lib.load()
-    fn, name = ((lib.gnn_sage_gather_concat_live_bf16, "gnn_sage_gather_concat_live_bf16")
-                if _bf16(table) else
-                (lib.gnn_sage_gather_concat_live_f32, "gnn_sage_gather_concat_live_f32"))
+    fn, name = _twin(_lib.load(), "gnn_sage_gather_concat_live", table)
     _lib.check(fn(
         table.data_ptr(), table.stride(0), table.shape[0], self_idx.data_ptr(), idx.data_ptr(),
         idx.stride(0), M, _lib.ptr(live), k, F, mode, out.data_ptr(),
@@ -1731,6 +1744,56 @@ class SageMapsT(NamedTuple):
     centre: bool = True
 
 
+def _maps_transpose(center_idx, neigh_idx, n_prev, check, centre):
+    """The body of ``sage_maps_transpose`` (``centre``: the M centre slots come first) and
+    ``sage_maps_transpose_nbr`` (``center_idx`` None: the neighbour map alone)."""
+    what = "sage_maps_transpose" if centre else "sage_maps_transpose_nbr"
+    _require_device(center_idx, neigh_idx)
+    if neigh_idx.dim() != 2:
+        raise ValueError("neigh_idx must be [M, k]")
+    if neigh_idx.dtype != torch.int64 or (centre and center_idx.dtype != torch.int64):
+        raise TypeError("the index maps must be int64")
+    n_prev = int(n_prev)
+    if n_prev < 0:
+        raise ValueError("n_prev must not be negative")
+    if ((neigh_idx.stride(1) != 1 and neigh_idx.shape[1] > 1)
+            or (neigh_idx.shape[0] > 1 and neigh_idx.stride(0) < neigh_idx.shape[1])):
+        neigh_idx = neigh_idx.contiguous()
+    M, k = neigh_idx.shape
+    if centre:
+        center_idx = center_idx.contiguous().view(-1)
+        if center_idx.numel() != M:
+            raise ValueError("center_idx must hold one index per row of neigh_idx")
+    dev = neigh_idx.device
+    n_slots = M * (k + 1 if centre else k)
+    if n_slots == 0:  # M = 0, or k = 0 without centre slots: every list is empty
+        return SageMapsT(torch.zeros(n_prev + 1, dtype=torch.int64, device=dev),
+                         torch.empty(0, dtype=torch.int32, device=dev), M, k, centre)
+    lib = _lib.load()
+    query = (lib.gnn_sage_maps_transpose_workspace_bytes if centre else
+             lib.gnn_sage_maps_transpose_nbr_workspace_bytes)
+    nbytes = int(query(M, k))
+    if nbytes == _lib.E_UNSUPPORTED or n_prev >= 2 ** 31 - 1:
+        return None
+    ptr = torch.empty(n_prev + 1, dtype=torch.int64, device=dev)
+    slot = torch.empty(n_slots, dtype=torch.int32, device=dev)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    err = _err_flag(dev, check)
+    # a single row's stride is never used; k = 0 (centre slots alone) reads no neighbour map
+    ldi = neigh_idx.stride(0) if M > 1 and k > 0 else k
+    nbr = neigh_idx.data_ptr() if k > 0 else None
+    tail = (ldi, M, k, n_prev, ptr.data_ptr(), slot.data_ptr(), err.data_ptr(), ws.data_ptr(),
+            ws.numel(), _lib.stream_handle(dev))
+    if centre:
+        rc = lib.gnn_sage_maps_transpose(center_idx.data_ptr(), nbr, *tail)
+    else:
+        rc = lib.gnn_sage_maps_transpose_nbr(nbr, *tail)
+    _lib.check(rc, "gnn_" + what)
+    if check:
+        _check_err(err, what)
+    return SageMapsT(ptr, slot, M, k, centre)
+
+
 def sage_maps_transpose(center_idx: torch.Tensor, neigh_idx: torch.Tensor, n_prev: int,
                         check: bool = True) -> SageMapsT | None:
     """The transposed maps of ``sage_gather_concat(table, center_idx, neigh_idx)`` over a table
@@ -1738,91 +1801,55 @@ def sage_maps_transpose(center_idx: torch.Tensor, neigh_idx: torch.Tensor, n_pre
     the slots by target): exactly numpy's stable argsort of ``[center_idx, neigh_idx.ravel()]``
     with its bincount / cumsum. ``check``: an index outside [0, n_prev) raises IndexError (one
     host read). None where M (k + 1) does not fit an int32 slot id."""
-    _require_device(center_idx, neigh_idx)
-    if neigh_idx.dim() != 2:
-        raise ValueError("neigh_idx must be [M, k]")
-    if center_idx.dtype != torch.int64 or neigh_idx.dtype != torch.int64:
-        raise TypeError("center_idx and neigh_idx must be int64")
-    n_prev = int(n_prev)
-    if n_prev < 0:
-        raise ValueError("n_prev must not be negative")
-    if ((neigh_idx.stride(1) != 1 and neigh_idx.shape[1] > 1)
-            or (neigh_idx.shape[0] > 1 and neigh_idx.stride(0) < neigh_idx.shape[1])):
-        neigh_idx = neigh_idx.contiguous()
-    center_idx = center_idx.contiguous().view(-1)
-    M, k = neigh_idx.shape
-    if center_idx.numel() != M:
-        raise ValueError("center_idx must hold one index per row of neigh_idx")
-    dev = neigh_idx.device
-    if M == 0:  # no slot: every list is empty
-        return SageMapsT(torch.zeros(n_prev + 1, dtype=torch.int64, device=dev),
-                         torch.empty(0, dtype=torch.int32, device=dev), 0, k)
-    lib = _lib.load()
-    nbytes = int(lib.gnn_sage_maps_transpose_workspace_bytes(M, k))
-    if nbytes == _lib.E_UNSUPPORTED or n_prev >= 2 ** 31 - 1:
-        return None
-    ptr = torch.empty(n_prev + 1, dtype=torch.int64, device=dev)
-    slot = torch.empty(M * (k + 1), dtype=torch.int32, device=dev)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    err = _err_flag(dev, check)
-    ldi = neigh_idx.stride(0) if M > 1 and k > 0 else k  # a single row's stride is never used
-    _lib.check(lib.gnn_sage_maps_transpose(
-        center_idx.data_ptr(), neigh_idx.data_ptr() if k > 0 else None, ldi, M, k, n_prev,
-        ptr.data_ptr(), slot.data_ptr(), err.data_ptr(), ws.data_ptr(), ws.numel(),
-        _lib.stream_handle(dev)), "gnn_sage_maps_transpose")
-    if check:
-        _check_err(err, "sage_maps_transpose")
-    return SageMapsT(ptr, slot, M, k)
+    return _maps_transpose(center_idx, neigh_idx, n_prev, check, True)
 
 
-def sage_scatter_concat(dbuf: torch.Tensor, tr: SageMapsT, n_prev: int,
-                        out: torch.Tensor | None = None) -> torch.Tensor | None:
-    """The adjoint of ``sage_gather_concat`` in MEAN mode (gnn_sage_scatter_concat_f32):
-    dX[t] = sum of dbuf[s, :F] over the centre slots s of t + sum of dbuf[m, F:] / k over the
-    neighbour slots (m, j) of t, for the maps ``tr = sage_maps_transpose(...)``; float32
-    [n_prev, F] with F = dbuf.shape[1] // 2. Rows nobody references are zeros. fp32 sums in
-    slot order, no float atomics: bit-identical from run to run. ``dbuf``: any float32 [M, 2F]
-    view with 16-B aligned rows; ``out``: a contiguous float32 [n_prev, F] tensor to write
-    (every row is stored, whatever it held). None where the kernel does not take the shape
-    (F not a power of two in [4, 256], k = 0, a misaligned view): the caller scatters another
-    way."""
-    _require_device(dbuf, tr.ptr, tr.slot, out)
-    if dbuf.dtype != torch.float32:
-        raise TypeError(f"dbuf must be float32 (got {dbuf.dtype})")
-    if dbuf.dim() != 2 or dbuf.shape[1] % 2:
-        raise ValueError("dbuf must be [M, 2F]")
-    n_prev = int(n_prev)
-    M, k = tr.M, tr.k
-    F = dbuf.shape[1] // 2
-    if (dbuf.shape[0] != M or tr.ptr.numel() != n_prev + 1 or tr.slot.numel() != M * (k + 1)
-            or not tr.centre):
-        raise ValueError("dbuf, the transposed maps and n_prev do not belong together")
-    if tr.ptr.dtype != torch.int64 or tr.slot.dtype != torch.int32:
-        raise TypeError("the transposed maps must be (int64 ptr, int32 slot)")
-    if out is not None and (out.shape != (n_prev, F) or out.dtype != torch.float32
-                            or not out.is_contiguous() or out.data_ptr() % 16):
-        raise ValueError(f"out must be a contiguous float32 [{n_prev}, {F}] tensor")
+def sage_maps_transpose_nbr(neigh_idx: torch.Tensor, n_prev: int,
+                            check: bool = True) -> SageMapsT | None:
+    """The transposed maps of ``sage_gather_aggregate(table, neigh_idx)`` over a table of
+    ``n_prev`` rows (gnn_sage_maps_transpose_nbr): ``sage_maps_transpose`` without the centre
+    slots -- slot e is the entry (e // k, e % k); exactly numpy's stable argsort of
+    ``neigh_idx.ravel()`` with its bincount / cumsum. The result has ``centre=False``.
+    ``check``: an index outside [0, n_prev) raises IndexError (one host read). None where M k
+    does not fit an int32 slot id."""
+    return _maps_transpose(None, neigh_idx, n_prev, check, False)
+
+
+def _gather_arg(table, self_idx, idx, check, centre):
+    """The body of ``sage_gather_concat_arg`` (``centre``: buf [M, 2F], the centre rows in its
+    first half) and ``sage_gather_aggregate_arg`` (``self_idx`` None: buf [M, F])."""
+    what = "sage_gather_concat_arg" if centre else "sage_gather_aggregate_arg"
+    table = _sage_table(table, "table", what, self_idx, idx)
+    idx = _sage_idx(idx)
+    M, k = idx.shape
+    F = table.shape[1]
+    if centre:
+        self_idx = _sage_self_idx(self_idx, M)
     lib = _lib.load()
-    if k == 0 or not lib.gnn_sage_scatter_concat_supported(F):
+    vec = 8 if _bf16(table) else 4
+    supported = (lib.gnn_sage_gather_concat_arg_supported if centre else
+                 lib.gnn_sage_gather_aggregate_arg_supported)
+    if not supported(F, k) or F % vec or table.stride(0) % vec or table.data_ptr() % 16:
         return None
+    ldb = 2 * F if centre else F
+    buf = torch.empty((M, ldb), dtype=torch.float32, device=table.device)
+    arg = torch.empty((M, F), dtype=torch.uint8, device=table.device)
     if M == 0:
-        return (torch.zeros((n_prev, F), dtype=torch.float32, device=dbuf.device)
-                if out is None else out.zero_())
-    if (dbuf.stride(1) != 1 or (M > 1 and (dbuf.stride(0) % 4 or dbuf.stride(0) < 2 * F))
-            or dbuf.data_ptr() % 16):
-        return None
-    nbytes = int(lib.gnn_sage_scatter_concat_workspace_bytes(M, k, F))
-    if nbytes < 0:
-        return None
-    dx = out if out is not None else torch.empty((n_prev, F), dtype=torch.float32,
-                                                 device=dbuf.device)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dbuf.device)
-    ptr, slot = tr.ptr.contiguous(), tr.slot.contiguous()
-    _lib.check(lib.gnn_sage_scatter_concat_f32(
-        dbuf.data_ptr(), dbuf.stride(0) if M > 1 else 2 * F, ptr.data_ptr(), slot.data_ptr(), M, k,
-        F, n_prev, dx.data_ptr(), F, ws.data_ptr(), ws.numel(),
-        _lib.stream_handle(dbuf.device)), "gnn_sage_scatter_concat_f32")
-    return dx
+        return buf, arg
+    err = _err_flag(table.device, check)
+    fn, name = _twin(lib, "gnn_" + what, table)
+    tail = (arg.data_ptr(), F, err.data_ptr(), _lib.stream_handle(table.device))
+    if centre:
+        rc = fn(table.data_ptr(), table.stride(0), table.shape[0], self_idx.data_ptr(),
+                idx.data_ptr(), idx.stride(0), M, k, F, buf.data_ptr(), ldb,
+                buf[:, F:].data_ptr(), ldb, *tail)
+    else:
+        rc = fn(table.data_ptr(), table.stride(0), table.shape[0], idx.data_ptr(), idx.stride(0),
+                M, k, F, buf.data_ptr(), ldb, *tail)
+    _lib.check(rc, name)
+    if check:
+        _check_err(err, what)
+    return buf, arg
 
 
 def sage_gather_concat_arg(table: torch.Tensor, self_idx: torch.Tensor, idx: torch.Tensor,
@@ -1837,40 +1864,100 @@ def sage_gather_concat_arg(table: torch.Tensor, self_idx: torch.Tensor, idx: tor
     (row, feature) instead of an int64. None where the kernel does not take the shape (F not a
     power of two in [4, 256] -- [8, 256] for a bfloat16 table --, k outside [1, 255], a table
     view whose rows are not 16-B lanes)."""
-    _f32_or_bf16(table, "table")
-    _require_device(table, self_idx, idx)
-    table = _rows_x(table, "table")
-    _bf16_inference_only(table, "sage_gather_concat_arg")
-    if idx.dim() != 2:
-        raise ValueError("idx must be [M, k]")
-    idx = idx.to(torch.int64)
-    if idx.stride(1) != 1:
-        idx = idx.contiguous()
-    self_idx = self_idx.to(torch.int64).contiguous().view(-1)
-    M, k = idx.shape
-    F = table.shape[1]
-    if self_idx.numel() != M:
-        raise ValueError("self_idx must hold one index per output row")
+    return _gather_arg(table, self_idx, idx, check, True)
+
+
+def sage_gather_aggregate_arg(table: torch.Tensor, idx: torch.Tensor, check: bool = True):
+    """``sage_gather_aggregate(table, idx, 'MAXPOOL')`` that also records the winner
+    (gnn_sage_gather_aggregate_arg_f32 / _bf16): returns ``(out, arg)`` -- out float32 [M, F] =
+    max_j table[idx[:, j]], arg uint8 [M, F] the winning neighbour column. The gcn-mode twin of
+    ``sage_gather_concat_arg`` (no centre half), with its rules: the first maximum, a NaN first
+    (``sage_gather_aggregate(table, idx, 'MAX')`` as bytes); out[m, f] is the value AT
+    arg[m, f]. None where the kernel does not take the shape (F not a power of two in [4, 256]
+    -- [8, 256] for a bfloat16 table --, k outside [1, 255], a table view whose rows are not
+    16-B lanes)."""
+    return _gather_arg(table, None, idx, check, False)
+
+
+def sage_scatter_supported(F: int) -> bool:
+    """Whether the scatters below take a table of width F: a power of two in [4, 256]
+    (gnn_sage_scatter_concat_supported; F / 4 lanes of 16 B per row)."""
+    return bool(_lib.load().gnn_sage_scatter_concat_supported(F))
+
+
+def _sage_scatter(dbuf, arg, tr, n_prev, out, centre, scale=None):
+    """The body of the four scatters. ``centre``: the concat layout (dbuf [M, 2F], the maps of
+    ``sage_maps_transpose``), else the gcn-mode one (dbuf [M, F], ``sage_maps_transpose_nbr``).
+    ``arg`` given: the MAXPOOL select; ``scale`` given (``sage_scatter_agg``): the scaled entry."""
+    _require_device(dbuf, arg, tr.ptr, tr.slot, out)
+    if dbuf.dtype != torch.float32:
+        raise TypeError(f"dbuf must be float32 (got {dbuf.dtype})")
+    if arg is not None and arg.dtype != torch.uint8:
+        raise TypeError(f"arg must be uint8 (got {arg.dtype})")
+    if dbuf.dim() != 2 or (centre and dbuf.shape[1] % 2):
+        raise ValueError("dbuf must be [M, 2F]" if centre else "dbuf must be [M, F]")
+    n_prev = int(n_prev)
+    M, k = tr.M, tr.k
+    width = dbuf.shape[1]  # of a row of dbuf: 2F with the centre half
+    F = width // 2 if centre else width
+    if (bool(tr.centre) != centre or dbuf.shape[0] != M or tr.ptr.numel() != n_prev + 1
+            or tr.slot.numel() != M * (k + 1 if centre else k)
+            or (arg is not None and tuple(arg.shape) != (M, F))):
+        raise ValueError("dbuf, arg, the transposed maps (sage_maps_transpose"
+                         f"{'' if centre else '_nbr'}) and n_prev do not belong together")
+    if tr.ptr.dtype != torch.int64 or tr.slot.dtype != torch.int32:
+        raise TypeError("the transposed maps must be (int64 ptr, int32 slot)")
+    if out is not None and (out.shape != (n_prev, F) or out.dtype != torch.float32
+                            or not out.is_contiguous() or out.data_ptr() % 16):
+        raise ValueError(f"out must be a contiguous float32 [{n_prev}, {F}] tensor")
     lib = _lib.load()
-    vec = 8 if _bf16(table) else 4
-    if (not lib.gnn_sage_gather_concat_arg_supported(F, k) or F % vec
-            or table.stride(0) % vec or table.data_ptr() % 16):
+    if k < 1 or (arg is not None and k > 255) or not lib.gnn_sage_scatter_concat_supported(F):
         return None
-    buf = torch.empty((M, 2 * F), dtype=torch.float32, device=table.device)
-    arg = torch.empty((M, F), dtype=torch.uint8, device=table.device)
     if M == 0:
-        return buf, arg
-    err = _err_flag(table.device, check)
-    fn, name = ((lib.gnn_sage_gather_concat_arg_bf16, "gnn_sage_gather_concat_arg_bf16")
-                if _bf16(table) else
-                (lib.gnn_sage_gather_concat_arg_f32, "gnn_sage_gather_concat_arg_f32"))
-    _lib.check(fn(
-        table.data_ptr(), table.stride(0), table.shape[0], self_idx.data_ptr(), idx.data_ptr(),
-        idx.stride(0), M, k, F, buf.data_ptr(), 2 * F, buf[:, F:].data_ptr(), 2 * F,
-        arg.data_ptr(), F, err.data_ptr(), _lib.stream_handle(table.device)), name)
-    if check:
-        _check_err(err, "sage_gather_concat_arg")
-    return buf, arg
+        return (torch.zeros((n_prev, F), dtype=torch.float32, device=dbuf.device)
+                if out is None else out.zero_())
+    if (dbuf.stride(1) != 1 or (M > 1 and (dbuf.stride(0) % 4 or dbuf.stride(0) < width))
+            or dbuf.data_ptr() % 16):
+        return None
+    if arg is not None and (arg.stride(1) != 1 or arg.data_ptr() % 4
+                            or (M > 1 and (arg.stride(0) % 4 or arg.stride(0) < F))):
+        return None
+    stem = (("gnn_sage_scatter_concat" if centre else "gnn_sage_scatter_agg")
+            + ("" if arg is None else "_maxpool"))
+    nbytes = int(getattr(lib, stem + "_workspace_bytes")(M, k, F))
+    if nbytes < 0:
+        return None
+    dx = out if out is not None else torch.empty((n_prev, F), dtype=torch.float32,
+                                                 device=dbuf.device)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dbuf.device)
+    ptr, slot = tr.ptr.contiguous(), tr.slot.contiguous()
+    ldd = dbuf.stride(0) if M > 1 else width  # a single row's stride is never used
+    if scale is not None:
+        _lib.run("gnn_sage_scatter_agg_scaled_f32", dbuf=dbuf.data_ptr(), ldd=ldd,
+                 ptr=ptr.data_ptr(), slot=slot.data_ptr(), M=M, k=k, feat=F, n_prev=n_prev,
+                 dx=dx.data_ptr(), ldx=F, scale=float(scale), workspace=ws.data_ptr(),
+                 workspace_bytes=ws.numel(), stream=_lib.stream_handle(dbuf.device))
+        return dx
+    mask = () if arg is None else (arg.data_ptr(), arg.stride(0) if M > 1 else F)
+    _lib.check(getattr(lib, stem + "_f32")(
+        dbuf.data_ptr(), ldd, *mask, ptr.data_ptr(), slot.data_ptr(), M, k, F, n_prev,
+        dx.data_ptr(), F, ws.data_ptr(), ws.numel(), _lib.stream_handle(dbuf.device)),
+        stem + "_f32")
+    return dx
+
+
+def sage_scatter_concat(dbuf: torch.Tensor, tr: SageMapsT, n_prev: int,
+                        out: torch.Tensor | None = None) -> torch.Tensor | None:
+    """The adjoint of ``sage_gather_concat`` in MEAN mode (gnn_sage_scatter_concat_f32):
+    dX[t] = sum of dbuf[s, :F] over the centre slots s of t + sum of dbuf[m, F:] / k over the
+    neighbour slots (m, j) of t, for the maps ``tr = sage_maps_transpose(...)``; float32
+    [n_prev, F] with F = dbuf.shape[1] // 2. Rows nobody references are zeros. fp32 sums in
+    slot order, no float atomics: bit-identical from run to run. ``dbuf``: any float32 [M, 2F]
+    view with 16-B aligned rows; ``out``: a contiguous float32 [n_prev, F] tensor to write
+    (every row is stored, whatever it held). None where the kernel does not take the shape
+    (F not a power of two in [4, 256], k = 0, a misaligned view): the caller scatters another
+    way."""
+    return _sage_scatter(dbuf, None, tr, n_prev, out, True)
 
 
 def sage_scatter_concat_maxpool(dbuf: torch.Tensor, arg: torch.Tensor, tr: SageMapsT,
@@ -1885,192 +1972,9 @@ def sage_scatter_concat_maxpool(dbuf: torch.Tensor, arg: torch.Tensor, tr: SageM
     run to run, every row of the result stored. ``arg``: a uint8 [M, F] view with unit column
     stride and rows of whole 4-B words. None where the kernel does not take the shape (the
     widths of ``sage_scatter_concat``, k outside [1, 255], a misaligned view)."""
-    _require_device(dbuf, arg, tr.ptr, tr.slot, out)
-    if dbuf.dtype != torch.float32:
-        raise TypeError(f"dbuf must be float32 (got {dbuf.dtype})")
-    if arg.dtype != torch.uint8:
-        raise TypeError(f"arg must be uint8 (got {arg.dtype})")
-    if dbuf.dim() != 2 or dbuf.shape[1] % 2:
-        raise ValueError("dbuf must be [M, 2F]")
-    n_prev = int(n_prev)
-    M, k = tr.M, tr.k
-    F = dbuf.shape[1] // 2
-    if (dbuf.shape[0] != M or tuple(arg.shape) != (M, F) or tr.ptr.numel() != n_prev + 1
-            or tr.slot.numel() != M * (k + 1) or not tr.centre):
-        raise ValueError("dbuf, arg, the transposed maps and n_prev do not belong together")
-    if tr.ptr.dtype != torch.int64 or tr.slot.dtype != torch.int32:
-        raise TypeError("the transposed maps must be (int64 ptr, int32 slot)")
-    if out is not None and (out.shape != (n_prev, F) or out.dtype != torch.float32
-                            or not out.is_contiguous() or out.data_ptr() % 16):
-        raise ValueError(f"out must be a contiguous float32 [{n_prev}, {F}] tensor")
-    lib = _lib.load()
-    if k < 1 or k > 255 or not lib.gnn_sage_scatter_concat_supported(F):
-        return None
-    if M == 0:
-        return (torch.zeros((n_prev, F), dtype=torch.float32, device=dbuf.device)
-                if out is None else out.zero_())
-    if (dbuf.stride(1) != 1 or (M > 1 and (dbuf.stride(0) % 4 or dbuf.stride(0) < 2 * F))
-            or dbuf.data_ptr() % 16 or arg.stride(1) != 1 or arg.data_ptr() % 4
-            or (M > 1 and (arg.stride(0) % 4 or arg.stride(0) < F))):
-        return None
-    nbytes = int(lib.gnn_sage_scatter_concat_maxpool_workspace_bytes(M, k, F))
-    if nbytes < 0:
-        return None
-    dx = out if out is not None else torch.empty((n_prev, F), dtype=torch.float32,
-                                                 device=dbuf.device)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dbuf.device)
-    ptr, slot = tr.ptr.contiguous(), tr.slot.contiguous()
-    _lib.check(lib.gnn_sage_scatter_concat_maxpool_f32(
-        dbuf.data_ptr(), dbuf.stride(0) if M > 1 else 2 * F, arg.data_ptr(),
-        arg.stride(0) if M > 1 else F, ptr.data_ptr(), slot.data_ptr(), M, k, F, n_prev,
-        dx.data_ptr(), F, ws.data_ptr(), ws.numel(), _lib.stream_handle(dbuf.device)),
-        "gnn_sage_scatter_concat_maxpool_f32")
-    return dx
-
-
-def sage_gather_aggregate_arg(table: torch.Tensor, idx: torch.Tensor, check: bool = True):
-    """``sage_gather_aggregate(table, idx, 'MAXPOOL')`` that also records the winner
-    (gnn_sage_gather_aggregate_arg_f32 / _bf16): returns ``(out, arg)`` -- out float32 [M, F] =
-    max_j table[idx[:, j]], arg uint8 [M, F] the winning neighbour column. The gcn-mode twin of
-    ``sage_gather_concat_arg`` (no centre half), with its rules: the first maximum, a NaN first
-    (``sage_gather_aggregate(table, idx, 'MAX')`` as bytes); out[m, f] is the value AT
-    arg[m, f]. None where the kernel does not take the shape (F not a power of two in [4, 256]
-    -- [8, 256] for a bfloat16 table --, k outside [1, 255], a table view whose rows are not
-    16-B lanes)."""
-    _f32_or_bf16(table, "table")
-    _require_device(table, idx)
-    table = _rows_x(table, "table")
-    _bf16_inference_only(table, "sage_gather_aggregate_arg")
-    if idx.dim() != 2:
-        raise ValueError("idx must be [M, k]")
-    idx = idx.to(torch.int64)
-    if idx.stride(1) != 1:
-        idx = idx.contiguous()
-    M, k = idx.shape
-    F = table.shape[1]
-    lib = _lib.load()
-    vec = 8 if _bf16(table) else 4
-    if (not lib.gnn_sage_gather_aggregate_arg_supported(F, k) or F % vec
-            or table.stride(0) % vec or table.data_ptr() % 16):
-        return None
-    out = torch.empty((M, F), dtype=torch.float32, device=table.device)
-    arg = torch.empty((M, F), dtype=torch.uint8, device=table.device)
-    if M == 0:
-        return out, arg
-    err = _err_flag(table.device, check)
-    fn, name = ((lib.gnn_sage_gather_aggregate_arg_bf16, "gnn_sage_gather_aggregate_arg_bf16")
-                if _bf16(table) else
-                (lib.gnn_sage_gather_aggregate_arg_f32, "gnn_sage_gather_aggregate_arg_f32"))
-    _lib.check(fn(
-        table.data_ptr(), table.stride(0), table.shape[0], idx.data_ptr(), idx.stride(0), M, k, F,
-        out.data_ptr(), F, arg.data_ptr(), F, err.data_ptr(), _lib.stream_handle(table.device)),
-        name)
-    if check:
-        _check_err(err, "sage_gather_aggregate_arg")
-    return out, arg
-
-
-def sage_maps_transpose_nbr(neigh_idx: torch.Tensor, n_prev: int,
-                            check: bool = True) -> SageMapsT | None:
-    """The transposed maps of ``sage_gather_aggregate(table, neigh_idx)`` over a table of
-    ``n_prev`` rows (gnn_sage_maps_transpose_nbr): ``sage_maps_transpose`` without the centre
-    slots -- slot e is the entry (e // k, e % k); exactly numpy's stable argsort of
-    ``neigh_idx.ravel()`` with its bincount / cumsum. The result has ``centre=False``.
-    ``check``: an index outside [0, n_prev) raises IndexError (one host read). None where M k
-    does not fit an int32 slot id."""
-    _require_device(neigh_idx)
-    if neigh_idx.dim() != 2:
-        raise ValueError("neigh_idx must be [M, k]")
-    if neigh_idx.dtype != torch.int64:
-        raise TypeError("neigh_idx must be int64")
-    n_prev = int(n_prev)
-    if n_prev < 0:
-        raise ValueError("n_prev must not be negative")
-    if ((neigh_idx.stride(1) != 1 and neigh_idx.shape[1] > 1)
-            or (neigh_idx.shape[0] > 1 and neigh_idx.stride(0) < neigh_idx.shape[1])):
-        neigh_idx = neigh_idx.contiguous()
-    M, k = neigh_idx.shape
-    dev = neigh_idx.device
-    if M == 0 or k == 0:  # no slot: every list is empty
-        return SageMapsT(torch.zeros(n_prev + 1, dtype=torch.int64, device=dev),
-                         torch.empty(0, dtype=torch.int32, device=dev), M, k, False)
-    lib = _lib.load()
-    nbytes = int(lib.gnn_sage_maps_transpose_nbr_workspace_bytes(M, k))
-    if nbytes == _lib.E_UNSUPPORTED or n_prev >= 2 ** 31 - 1:
-        return None
-    ptr = torch.empty(n_prev + 1, dtype=torch.int64, device=dev)
-    slot = torch.empty(M * k, dtype=torch.int32, device=dev)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    err = _err_flag(dev, check)
-    ldi = neigh_idx.stride(0) if M > 1 else k  # a single row's stride is never used
-    _lib.check(lib.gnn_sage_maps_transpose_nbr(
-        neigh_idx.data_ptr(), ldi, M, k, n_prev, ptr.data_ptr(), slot.data_ptr(), err.data_ptr(),
-        ws.data_ptr(), ws.numel(), _lib.stream_handle(dev)), "gnn_sage_maps_transpose_nbr")
-    if check:
-        _check_err(err, "sage_maps_transpose_nbr")
-    return SageMapsT(ptr, slot, M, k, False)
-
-
-def _scatter_agg(dbuf, arg, tr, n_prev, out, scale=None):
-    """``sage_scatter_agg`` (arg None; ``scale`` given: the scaled entry) /
-    ``sage_scatter_agg_maxpool``."""
-    _require_device(dbuf, arg, tr.ptr, tr.slot, out)
-    if dbuf.dtype != torch.float32:
-        raise TypeError(f"dbuf must be float32 (got {dbuf.dtype})")
-    if arg is not None and arg.dtype != torch.uint8:
-        raise TypeError(f"arg must be uint8 (got {arg.dtype})")
-    if dbuf.dim() != 2:
-        raise ValueError("dbuf must be [M, F]")
-    n_prev = int(n_prev)
-    M, k = tr.M, tr.k
-    F = dbuf.shape[1]
-    if (tr.centre or dbuf.shape[0] != M or tr.ptr.numel() != n_prev + 1
-            or tr.slot.numel() != M * k or (arg is not None and tuple(arg.shape) != (M, F))):
-        raise ValueError("dbuf, arg, the transposed maps (sage_maps_transpose_nbr) and n_prev do "
-                         "not belong together")
-    if tr.ptr.dtype != torch.int64 or tr.slot.dtype != torch.int32:
-        raise TypeError("the transposed maps must be (int64 ptr, int32 slot)")
-    if out is not None and (out.shape != (n_prev, F) or out.dtype != torch.float32
-                            or not out.is_contiguous() or out.data_ptr() % 16):
-        raise ValueError(f"out must be a contiguous float32 [{n_prev}, {F}] tensor")
-    lib = _lib.load()
-    if k < 1 or (arg is not None and k > 255) or not lib.gnn_sage_scatter_concat_supported(F):
-        return None
-    if M == 0:
-        return (torch.zeros((n_prev, F), dtype=torch.float32, device=dbuf.device)
-                if out is None else out.zero_())
-    if (dbuf.stride(1) != 1 or (M > 1 and (dbuf.stride(0) % 4 or dbuf.stride(0) < F))
-            or dbuf.data_ptr() % 16):
-        return None
-    if arg is not None and (arg.stride(1) != 1 or arg.data_ptr() % 4
-                            or (M > 1 and (arg.stride(0) % 4 or arg.stride(0) < F))):
-        return None
-    query = (lib.gnn_sage_scatter_agg_workspace_bytes if arg is None else
-             lib.gnn_sage_scatter_agg_maxpool_workspace_bytes)
-    nbytes = int(query(M, k, F))
-    if nbytes < 0:
-        return None
-    dx = out if out is not None else torch.empty((n_prev, F), dtype=torch.float32,
-                                                 device=dbuf.device)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dbuf.device)
-    ptr, slot = tr.ptr.contiguous(), tr.slot.contiguous()
-    ldd = dbuf.stride(0) if M > 1 else F
-    if arg is None and scale is not None:
-        _lib.run("gnn_sage_scatter_agg_scaled_f32", dbuf=dbuf.data_ptr(), ldd=ldd,
-                 ptr=ptr.data_ptr(), slot=slot.data_ptr(), M=M, k=k, feat=F, n_prev=n_prev,
-                 dx=dx.data_ptr(), ldx=F, scale=float(scale), workspace=ws.data_ptr(),
-                 workspace_bytes=ws.numel(), stream=_lib.stream_handle(dbuf.device))
-    elif arg is None:
-        _lib.check(lib.gnn_sage_scatter_agg_f32(
-            dbuf.data_ptr(), ldd, ptr.data_ptr(), slot.data_ptr(), M, k, F, n_prev, dx.data_ptr(),
-            F, ws.data_ptr(), ws.numel(), _lib.stream_handle(dbuf.device)),
-            "gnn_sage_scatter_agg_f32")
-    else:
-        _lib.check(lib.gnn_sage_scatter_agg_maxpool_f32(
-            dbuf.data_ptr(), ldd, arg.data_ptr(), arg.stride(0) if M > 1 else F, ptr.data_ptr(),
-            slot.data_ptr(), M, k, F, n_prev, dx.data_ptr(), F, ws.data_ptr(), ws.numel(),
-            _lib.stream_handle(dbuf.device)), "gnn_sage_scatter_agg_maxpool_f32")
-    return dx
+    if arg is None:
+        raise TypeError("arg must be a uint8 [M, F] tensor")
+    return _sage_scatter(dbuf, arg, tr, n_prev, out, True)
 
 
 def sage_scatter_agg(dbuf: torch.Tensor, tr: SageMapsT, n_prev: int,
@@ -2087,7 +1991,7 @@ def sage_scatter_agg(dbuf: torch.Tensor, tr: SageMapsT, n_prev: int,
     ``scale``: the factor in place of 1 / k (gnn_sage_scatter_agg_scaled_f32): 1 for the adjoint
     of a SUM over the neighbours or of a row gather (k = 1); ``scale = 1 / k`` (in float32) gives
     the default's result bit for bit."""
-    return _scatter_agg(dbuf, None, tr, n_prev, out, scale)
+    return _sage_scatter(dbuf, None, tr, n_prev, out, False, scale)
 
 
 def sage_scatter_agg_maxpool(dbuf: torch.Tensor, arg: torch.Tensor, tr: SageMapsT, n_prev: int,
@@ -2101,7 +2005,7 @@ def sage_scatter_agg_maxpool(dbuf: torch.Tensor, arg: torch.Tensor, tr: SageMaps
     ``sage_scatter_agg``, k outside [1, 255], a misaligned view)."""
     if arg is None:
         raise TypeError("arg must be a uint8 [M, F] tensor")
-    return _scatter_agg(dbuf, arg, tr, n_prev, out)
+    return _sage_scatter(dbuf, arg, tr, n_prev, out, False)
 
 
 def sage_train_layer_supported(table: torch.Tensor, weight: torch.Tensor, k: int,
@@ -2123,7 +2027,7 @@ def sage_train_layer_supported(table: torch.Tensor, weight: torch.Tensor, k: int
     lib = _lib.load()
     ok = bool(K == (F if gcn else 2 * F) and lib.gnn_gcn_transform_supported(K, H)
               and (TRANSFORM_WIDE_MFMA or not (H == 256 and K > 64))
-              and lib.gnn_sage_scatter_concat_supported(F))
+              and sage_scatter_supported(F))
     if ok and agg == 'MAXPOOL':
         vec = 8 if table.dtype == torch.bfloat16 else 4
         sup = (lib.gnn_sage_gather_aggregate_arg_supported if gcn else
@@ -2587,13 +2491,9 @@ def sage_layer(table: torch.Tensor, nbr_idx: torch.Tensor, weight: torch.Tensor,
     if not lib.gnn_sage_layer_supported(feat, H):
         return None
     w = weight.detach().to(torch.float32).contiguous()
-    nbr_idx = nbr_idx.to(torch.int64)
-    if nbr_idx.stride(1) != 1:
-        nbr_idx = nbr_idx.contiguous()
+    nbr_idx = _sage_idx(nbr_idx)
     if self_idx is not None:
-        self_idx = self_idx.to(torch.int64).contiguous().view(-1)
-        if self_idx.numel() != M:
-            raise ValueError("self_idx must hold one index per output row")
+        self_idx = _sage_self_idx(self_idx, M)
     out = torch.empty((M, H), dtype=torch.float32, device=table.device)
     err = _err_flag(table.device, check)
     _lib.check(lib.gnn_sage_layer_f32(
@@ -2612,10 +2512,7 @@ def gather_rows(x: torch.Tensor, idx: torch.Tensor, out: torch.Tensor | None = N
     table's dtype, as torch.embedding's: a bfloat16 table gives bfloat16 rows
     (gnn_gather_rows_bf16); a float32 ``out=`` view of a bfloat16 table selects the widening
     gather (gnn_gather_rows_bf16_f32: ``x[idx].float()`` in the same launch)."""
-    _f32_or_bf16(x, "x")
-    _require_device(x, idx, out)
-    x = _rows_x(x, "x")
-    _bf16_inference_only(x, "gather_rows")
+    x = _sage_table(x, "x", "gather_rows", idx, out)
     idx = idx.to(torch.int64).contiguous().view(-1)
     n, F = idx.numel(), x.shape[1]
     if out is None:
